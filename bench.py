@@ -1,6 +1,6 @@
 """bench.py -- self-play throughput of the MI355X engine on BASELINE.json's configurations.
 
-    python bench.py [--workload connect4|brandubh|arena|trimok] --gpus N --steps K --warmup W
+    python bench.py [--workload connect4|brandubh|arena|trimok] --gpus N --steps K --warmup W [--dump-outputs DIR] [--other-workloads]
 
 Default workload = the headline config (BASELINE.json configs[1]): connect4, 2048 concurrent games per GPU x 100 MCTS sims per
 move, fp16 ResNet 128ch x 8 (envs/connect4/train.py net + search hyper-parameters), random-init weights, games from the empty
@@ -16,6 +16,11 @@ Measured inside the run (HIP events on the launch stream, rounds launched eagerl
 `roofline` = the dominant kernel of a simulation step, `tree_roofline` = the tree launch.  `traffic` (HBM bytes per launch) comes
 from the committed rocprofv3 --pmc summary profiles/r03_pmc.json (tools/collect_profiles.py, run on the GPU box), never from a
 constant in this file.  `cpu_baseline` (rank 0, N = 1 only) = the C oracle on the host cores, bounded sample.
+
+The result is ONE JSON line, the last line on stdout.  `ms_per_step` = the timed region's wall time over --steps (exactly --steps
+rounds run in it).  `--other-workloads` adds configs 3-5, their shard sizes and compat mode to the connect4 line (a much longer run
+and line).  `--dump-outputs DIR` writes what the timed path handed its caller after the last timed step as DIR/<name>.npy
+(dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -344,7 +349,40 @@ def timed_region(c, steps, warmup, world, rank):
                 late += 1
     late = int(D.all_reduce_tallies([late])[0])
     r['games_second_half'], r['second_half_steps'] = late, half
+    r['exchange'] = ex
     return r
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(c, t, directory, budget=DUMP_BUDGET_BYTES):
+    """What the timed path handed its caller after the last timed step, as DIR/<name>.npy (float32 / float64, <= `budget` bytes):
+      tallies            float64: the exchange step's counts -- self-play: wins per player, draws, num_results, games, expansions,
+                         sims, num_samples; arena: wins per model, draws, num_results, games, expansions, sims
+      last_actions       float64 [B]: the move every slot of this rank played in the last timed round
+      samples_obs / _pi / _z   float32 (self-play): the gathered training examples the exchange step returned, in output order;
+                         above the budget a fixed seeded subset of rows (ascending), whose row numbers are samples_rows (float64)
+    Written right after the timed region, before anything else runs on the engines."""
+    os.makedirs(directory, exist_ok=True)
+    ex = t['exchange']
+    keys = ['wins', 'draws', 'num_results', 'games', 'expansions', 'sims'] + ([] if c.arena else ['num_samples'])
+    arrays = {'tallies': np.array([float(x) for k in keys for x in (ex[k] if isinstance(ex[k], list) else [ex[k]])], np.float64),
+              'last_actions': torch.cat([e.last_actions() for e in c.engines]).cpu().numpy().astype(np.float64)}
+    if not c.arena:
+        obs, pi, z = (x.float().cpu().numpy() for x in ex['samples'])
+        n = obs.shape[0]
+        row = max(obs[:1].nbytes + pi[:1].nbytes + z[:1].nbytes, 1)
+        room = budget - sum(a.nbytes for a in arrays.values()) - (1 << 20)      # (headroom for the row numbers and .npy headers)
+        if n * row > room:
+            k = room // (row + 8)
+            rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+            obs, pi, z = obs[rows], pi[rows], z[rows]
+            arrays['samples_rows'] = rows.astype(np.float64)
+        arrays.update(samples_obs=np.ascontiguousarray(obs), samples_pi=np.ascontiguousarray(pi), samples_z=np.ascontiguousarray(z))
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), arr)
+    return {name: list(arr.shape) for name, arr in arrays.items()}
 
 
 def profile_rounds(c, persistent_rounds=10):
@@ -693,16 +731,21 @@ def main():
     ap.add_argument('--no-library-gemm', action='store_true', help='skip the hipBLASLt context GEMM (keeps profiler traces to our own kernels)')
     ap.add_argument('--no-fused-search', action='store_true',
                     help='2 launches per simulation (tower, backup+select) instead of one persistent launch per move (azg_search_f16)')
-    ap.add_argument('--no-other-workloads', action='store_true',
-                    help='skip the short runs of BASELINE configs 3-5 that the default (connect4, 1 GPU) line carries as other_workloads')
+    ap.add_argument('--other-workloads', action='store_true',
+                    help='connect4, 1 GPU: also time BASELINE configs 3-5, their shard sizes and compat mode (other_workloads, strong_scaling_shards)')
+    ap.add_argument('--no-other-workloads', action='store_true', help='(the default; kept for older command lines)')
     ap.add_argument('--profile-rounds', type=int, default=10, help='eager rounds of the persistent launch timed after the timed region')
     ap.add_argument('--compat', action='store_true', help='also time compat mode (unmodified-Coach protocol: SelfPlayAgent processes served by the parent)')
     ap.add_argument('--search-heads', default=None, choices=['exact', 'sparse'],
                     help='wide-head workloads, persistent launch: all A + P+1 logits inside the launch (bit-exact) or the valid actions only')
     ap.add_argument('--no-exact-heads', '--no-sparse-heads', dest='no_sparse_heads', action='store_true',
                     help='skip the second run of the wide-head workloads with the opt-in sparse heads')
-    ap.add_argument('--no-shards', action='store_true', help='skip the 1 / 2 / 4-GPU shard sizes of configs 3-5 on the default line')
+    ap.add_argument('--no-shards', action='store_true', help='with --other-workloads: skip the 1 / 2 / 4-GPU shard sizes of configs 3-5')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path returned after its last step as DIR/<name>.npy (float32 / float64, <= 64 MB)')
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return self_launch(a.gpus)                                    # one rank per GPU under torch.distributed.run
@@ -717,6 +760,8 @@ def main():
 
     c = build(a.workload, a, rank, local_rank, dev, a.steps + a.warmup + a.profile_rounds + 8)
     t = timed_region(c, a.steps, a.warmup, world, rank)
+    dumped = dump_outputs(c, t, a.dump_outputs) if a.dump_outputs and rank == 0 else None   # (before anything else runs on the engines)
+    t.pop('exchange')
     netprof, prof = profile_rounds(c, a.profile_rounds)              # after the timed region
     ex = None if a.no_sparse_heads else sparse_heads_run(c, a, rank, local_rank, dev, world)   # (every rank: it has its own exchange step)
     if rank != 0:
@@ -757,7 +802,9 @@ def main():
         roofline['vs_library_gemm'] = round(roofline['achieved'] / lib_tf, 3)
     if world == 1 and not a.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(c.W, c.nets, c.arena)
-    if world == 1 and a.workload == 'connect4' and not a.no_other_workloads and not a.slots:
+    if dumped is not None:
+        out['dumped_outputs'] = dumped
+    if world == 1 and a.workload == 'connect4' and a.other_workloads and not a.slots:
         # BASELINE configs 3-5 at their per-GPU size: 8 graph-replayed rounds each after 2 warm-up rounds (their own full lines:
         # --workload NAME; profiles/r03_bench_*.json)
         release(c)
@@ -823,7 +870,8 @@ def main():
             out['projected_scaling'] = projected_scaling(out, others, shards)
     elif world == 1 and a.compat and not c.arena:
         out['compat'] = compat_run(c.W, c.net)
-    print(json.dumps(out))
+    sys.stderr.flush()
+    print(json.dumps(out), flush=True)
     return 0
 
 

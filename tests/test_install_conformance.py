@@ -1,7 +1,8 @@
 """Row (b) of SURVEY.md section 8, pinned against drift: after `alphazero_general_amd.install()` the reference's own callers resolve
 to this package's classes, and those classes keep the reference's call signatures.
 
-Runs only where the reference is present (the build container; /root/reference does not exist on the GPU box): a subprocess
+The signatures are held to tests/golden/ref_signatures.json (tests/golden/make_ref_signatures.py), everywhere.  The rest runs only where
+the reference is present (the build container; /root/reference does not exist on the GPU box): the record is checked against the source, and a subprocess
 imports the real `alphazero` package (pyximport, tensorboardX stubbed -- the recipe of tests/golden/refharness.py) AFTER install()
 and reports what `alphazero.Coach.SelfPlayAgent`, `alphazero.Arena.SelfPlayAgent` and `alphazero.GenericPlayers.MCTS` are bound to
 (import sites Coach.py:5, Arena.pyx:4, GenericPlayers.py:1).  The signatures are read from the reference's SOURCE TEXT
@@ -17,7 +18,8 @@ import pytest
 
 REF = '/root/reference'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'alphazero')), reason='needs the reference checkout (build container only)')
+needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'alphazero')), reason='needs the reference checkout (build container only)')
+RECORD = os.path.join(ROOT, 'tests', 'golden', 'ref_signatures.json')
 
 C_TYPES = {'object', 'int', 'bint', 'float', 'double', 'Py_ssize_t', 'float[:]', 'int[:]', 'np.ndarray'}
 
@@ -52,14 +54,27 @@ def _our_signature(fn):
     return out
 
 
+def _recorded(cls):
+    """the reference's signatures of `cls` as recorded in tests/golden/ref_signatures.json, in _ref_signatures' form"""
+    with open(RECORD) as fh:
+        return {m: [tuple(p) for p in ps] for m, ps in json.load(fh)[cls].items()}
+
+
+@needs_reference
+def test_signature_record_matches_the_reference_source():
+    ref = os.path.join(REF, 'alphazero')
+    assert _recorded('SelfPlayAgent') == _ref_signatures(os.path.join(ref, 'SelfPlayAgent.pyx'), 'SelfPlayAgent')
+    assert _recorded('MCTS') == _ref_signatures(os.path.join(ref, 'MCTS.pyx'), 'MCTS')
+
+
 def test_signatures_match_the_reference_source():
     from alphazero_general_amd.MCTS import MCTS
     from alphazero_general_amd.SelfPlayAgent import SelfPlayAgent
-    ref_agent = _ref_signatures(os.path.join(REF, 'alphazero', 'SelfPlayAgent.pyx'), 'SelfPlayAgent')
+    ref_agent = _recorded('SelfPlayAgent')
     assert _our_signature(SelfPlayAgent.__init__) == ref_agent['__init__']                      # SelfPlayAgent.pyx:14-16
     for meth in ('run', 'generateBatch', 'processBatch', 'playMoves'):                          # :79,103,137,153
         assert _our_signature(getattr(SelfPlayAgent, meth)) == ref_agent[meth], meth
-    ref_mcts = _ref_signatures(os.path.join(REF, 'alphazero', 'MCTS.pyx'), 'MCTS')
+    ref_mcts = _recorded('MCTS')
     public = ['__init__', 'reset', 'search', 'raw_search', 'update_root', 'find_leaf', 'process_results', 'counts', 'best_action',
               'probs', 'value']                                                                  # MCTS.pyx:133-344
     for meth in public:
@@ -102,6 +117,7 @@ print(json.dumps(dict(
 '''
 
 
+@needs_reference
 def test_install_rebinds_the_reference_callers():
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
     r = subprocess.run([sys.executable, '-c', _PROBE % dict(root=ROOT, ref=REF)], capture_output=True, text=True, timeout=900, env=env)
@@ -170,6 +186,7 @@ print(json.dumps(out))
 """
 
 
+@needs_reference
 def test_games_without_device_rules_fall_through_to_the_reference():
     """SURVEY.md 8b "Game plugin": after install() an env without device rule kernels (tictactoe) keeps working -- the MCTS /
     SelfPlayAgent classes registered under the reference's names hand it to the REFERENCE'S OWN classes (same trees as calling the
@@ -229,6 +246,7 @@ print(json.dumps(out))
 """
 
 
+@needs_reference
 def test_reference_game_objects_encode_and_decode():
     """GenericPlayers hands `MCTS.search` / `find_leaf` the REFERENCE'S own Game objects (connect4.pyx, brandubh/fastafl.pyx) and expects
     leaves of the same class back (MCTS.pyx:208-228): their state must cross the ABI both ways -- same azg_state as this package's

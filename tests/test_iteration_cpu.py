@@ -298,3 +298,22 @@ def test_adapter_against_the_real_coach(tmp_path):
     assert t['losses'] == [0.5, 0.25] and t['saved'] == 'iteration-0001.pkl'
     assert d['scalars'] == [['win_rate/player0', round(3.5 / 6, 4), 1], ['win_rate/player1', round(2.5 / 6, 4), 1], ['win_rate/draws', round(1 / 6, 4), 1],
                             ['win_rate/avg_game_length', 20.5, 1]]
+
+
+def test_adapter_against_the_recorded_coach():
+    """the part of test_adapter_against_the_real_coach that needs no reference checkout: the adapter defines the five self-play methods
+    with the parameter lists of the reference's Coach (tests/golden/ref_signatures.json, make_ref_signatures.py), overrides nothing
+    else but learn, and the record holds learn()'s call order (Coach.py:252-267) and the methods' lines (:291,326,364,389,401)."""
+    import inspect
+    from alphazero_general_amd.coach import native_coach
+    with open(os.path.join(ROOT, 'tests', 'golden', 'ref_signatures.json')) as fh:
+        rec = json.load(fh)['Coach']
+    lines = {'generateSelfPlayAgents': 291, 'processSelfPlayBatches': 326, 'saveIterationSamples': 364, 'processGameResults': 389, 'killSelfPlayAgents': 401}
+    assert rec['learn_calls'] == list(lines) and {m: r['line'] for m, r in rec['five'].items()} == lines
+
+    class Coach:                                                      # a stand-in base: the adapter's own methods are what is checked
+        pass
+    Native = native_coach(Coach, install_arena=False)
+    for m, r in rec['five'].items():
+        assert m in Native.__dict__ and list(inspect.signature(Native.__dict__[m]).parameters) == r['params'], (m, r)
+    assert sorted(k for k in Native.__dict__ if not k.startswith('_')) == sorted(list(lines) + ['learn'])
