@@ -23,6 +23,15 @@ def check_probs(name, p, rp, v, rv, tol=TOL):
     rec = {'test': name, 'boards': int(p.shape[0]), 'max_abs_policy': float((p - rp).abs().max()), 'max_abs_value': float((v - rv).abs().max()),
            'kl_policy': kl(rp, p), 'kl_value': kl(rv, v), 'tolerance': tol}
     print('NNERR ' + json.dumps(rec))
+    record_error(rec)
+    assert rec['max_abs_policy'] < tol and rec['max_abs_value'] < tol, rec
+    return rec
+
+
+def record_error(rec):
+    """append one measured-error record to the network error log (nn_error.jsonl) that DESIGN.md quotes; shared by the network tests"""
+    import json
+    import os
     try:
         out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out')
         os.makedirs(out, exist_ok=True)
@@ -30,8 +39,6 @@ def check_probs(name, p, rp, v, rv, tol=TOL):
             f.write(json.dumps(rec) + '\n')
     except OSError:
         pass
-    assert rec['max_abs_policy'] < tol and rec['max_abs_value'] < tol, rec
-    return rec
 
 
 def _randomize(net, torch, seed=0):
