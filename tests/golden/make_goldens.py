@@ -5,6 +5,8 @@ Outputs (small .npz fixtures, committed):
   c4_rules.npz   connect4 rule tables: random playouts -> valid_moves / board / win_state / observation
   c4_tree.npz    single-tree MCTS traces (find_leaf paths, per-sim root stats, counts / probs / value)
   c4_agent.npz   SelfPlayAgent lock-step self-play traces (actions, leaf-obs checksums, samples, results)
+  {c4,br,tm}_edge.npz  the tree edge family (gen_edge): tests/edge_eval.py rows at PUCT ties, zero / denormal priors, exact draws,
+                 configuration extremes and roots with 1, 2, 63-65 children; per-simulation paths and root rows, final records, coverage counts
   c4_mt19937.npz MCTS.search under np.random.seed(s) on numpy's own MT19937 stream: recorded child shuffles + counts / pi (second tier)
   c4_mt19937_agent.npz, br_mt19937_agent.npz   a whole SelfPlayAgent (noise + temperature on) under np.random.seed(s): every shuffle /
                  dirichlet / choice draw observed per game slot + what the agent did (connect4: 6 games; brandubh: 4 games, 53 rounds)
@@ -361,8 +363,9 @@ AGENT_CONFIGS = [
 ]
 
 
-def run_ref_agent(game_cls, game_id, cname, B, sims, games, kw, seed, slot_base=0, is_arena=False, max_rounds=400):
+def run_ref_agent(game_cls, game_id, cname, B, sims, games, kw, seed, slot_base=0, is_arena=False, max_rounds=400, evaluator=None):
     import torch
+    evaluator = evaluator or ol.fake_eval
     gi = ol.game_info(game_id)
     A, NV = gi.action_size, gi.num_players + 1
     is_warmup = cname == 'warmup'
@@ -390,12 +393,12 @@ def run_ref_agent(game_cls, game_id, cname, B, sims, games, kw, seed, slot_base=
                         rec['obs_crc'].append([rh.crc(rows[i].numpy()) for i in range(B)])
                         rec.setdefault('row_game', []).append(list(ag.batch_indices))
                         for row in range(B):
-                            p, v = ol.fake_eval(seed, slot_base + ag.batch_indices[row], step, A, NV)
+                            p, v = evaluator(seed, slot_base + ag.batch_indices[row], step, A, NV)
                             ag.policy_tensor[row] = torch.from_numpy(p); ag.value_tensor[row] = torch.from_numpy(v)
                     else:
                         rec['obs_crc'].append([rh.crc(ag.batch_tensor[i].numpy()) for i in range(B)])
                         for i in range(B):
-                            p, v = ol.fake_eval(seed, slot_base + i, step, A, NV)
+                            p, v = evaluator(seed, slot_base + i, step, A, NV)
                             ag.policy_tensor[i] = torch.from_numpy(p); ag.value_tensor[i] = torch.from_numpy(v)
                 ag.processBatch()
                 step += 1
@@ -586,6 +589,268 @@ def gen_ckpt():
     print('c4_ckpt: %d bytes' % os.path.getsize(os.path.join(OUT, 'c4_ref_checkpoint.pth.tar')))
 
 
+# ------------------------------------------------------------------------------------------------- edge family
+# The tree code's edges, observed on the reference itself: exact PUCT ties, zero priors, the two forms of the seen-policy sum,
+# exact draw values, cpuct / fpu / noise / temperature extremes, roots with 1, 2 and 63-65 children.  The evaluators are
+# tests/edge_eval.py; every row fed is recorded as a crc.
+EDGE_CONFIGS = [
+    # name, evaluator family, cpuct, fpu_reduction, root noise_frac (0: off), root temperature (0: off)
+    ('uniform_q', 'uniform', 0.0, 0.0, 0.0, 0.0),          # pure Q: every unvisited child ties at fpu, every visited one at q
+    ('uniform_bonus', 'uniform', 1.25, -1.0, 0.0, 2.0),    # first-play bonus; root temperature 2 (numpy's ** 0.5 path)
+    ('dyadic', 'dyadic', 1.25, 0.4, 0.0, 0.0),
+    ('dyadic_noise1', 'dyadic', 50.0, 0.0, 1.0, 0.5),      # noise replaces the root priors; temperature 0.5 (** 2)
+    ('onehot', 'onehot', 1.25, 0.4, 0.1, 0.0),
+    ('onehot_q', 'onehot', 0.0, -1.0, 0.0, 2.0),
+    ('spread', 'spread', 1.25, -1.0, 0.0, 0.0),            # (the bonus visits every child: wide seen-policy sums)
+    ('spread_powf', 'spread', 50.0, 0.4, 0.1, 1.1),        # the powf tier
+]
+EDGE_PROB_TEMPS = [1.0, 2.0, 0.5, 0.1, 0.0, 0.01]          # 0.01: (counts / n) ** 100 underflows
+EDGE_GAMES = {                                             # name: (game id, random roots, sims, edge root move counts)
+    'c4': (ol.GAME_CONNECT4, 12, 60, (1, 2)),
+    'tm': (ol.GAME_TRIMOK, 12, 48, (1, 2)),
+    'br': (ol.GAME_BRANDUBH, 6, 40, (63, 64, 65)),
+}
+EDGE_COV = ['best_child_calls', 'tied_max', 'zero_prior_selected', 'seen_sum_tree', 'seen_sum_serial_wide', 'draw_backups', 'underflows']
+EDGE_FLOORS = {                                            # per game, summed over the configs
+    'tied_max': 500, 'zero_prior_selected': 50, 'seen_sum_tree': 100, 'seen_sum_serial_wide': 50, 'draw_backups': 100,
+}
+
+
+def _edge_game_cls(name):
+    if name == 'c4':
+        from alphazero.envs.connect4.connect4 import Game
+        return Game
+    if name == 'br':
+        return br_game_cls()
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from alphazero_general_amd.envs.trimok import Game
+    return Game
+
+
+def _ref_cells(name, g):
+    if name == 'c4':
+        return c4_ref_to_cells(g)
+    if name == 'br':
+        return br_state(g)[0]
+    return np.asarray(g._board, np.int8).reshape(-1)
+
+
+def _edge_roots(name, game_cls, gid, n_random, ks, seed):
+    """reference game objects at the roots: random legal prefixes, then positions whose side to move has exactly k moves (found by
+    playouts, or for brandubh's k > 63 -- playouts from the start stay at <= 63 -- crafted as in oracle_lib.br_wide_positions)"""
+    rng = np.random.RandomState(seed)
+    roots, kinds = [], []
+    for r in range(n_random):
+        g = game_cls()
+        for _ in range(0 if r == 0 else rng.randint(0, 30)):
+            v = np.flatnonzero(np.asarray(g.valid_moves()))
+            g2 = g.clone(); g2.play_action(int(rng.choice(v)))
+            if np.asarray(g2.win_state()).any():
+                break
+            g = g2
+        roots.append(g); kinds.append(0)
+    for k in ks:
+        found = None
+        for _ in range(200000 if k <= 63 else 0):          # playouts until the side to move has k moves
+            o, seq = ol.OGame(gid), []
+            while not o.win_state().any():
+                v = np.flatnonzero(o.valid_moves())
+                if len(v) == k:
+                    found = seq
+                    break
+                a = int(rng.choice(v)); o.play(a); seq.append(a)
+            if found is not None:
+                break
+        if found is not None:
+            g = game_cls()
+            for a in found:
+                g.play_action(a)
+        else:
+            assert name == 'br'
+            g = None
+            for _ in range(400000):
+                c = np.zeros(49, np.int8); c[[0, 6, 42, 48]] = 5; c[24] = 4
+                free = np.flatnonzero(c == 0)
+                pick = rng.choice(free, 9 + rng.randint(0, 3), replace=False)
+                c[pick[:8]] = 2; c[pick[8]] = 3; c[pick[9:]] = 1
+                st = ol.State()
+                for i in range(49):
+                    st.cells[i] = int(c[i])
+                o = ol.OGame(gid, state=st)
+                if o.win_state().any() or int(o.valid_moves().sum()) != k:
+                    continue
+                g = game_cls()
+                g._board._state = np.array(c.reshape(7, 7), dtype=g._board._state.dtype)    # as the reference's own symmetries() does
+                break
+            assert g is not None, k
+        assert int(np.asarray(g.valid_moves()).sum()) == k and not np.asarray(g.win_state()).any(), (name, k)
+        roots.append(g); kinds.append(k)
+    return roots, kinds
+
+
+def _root_state(name, gid, g):
+    """the oracle's state of a reference root, checked cell for cell, valid move for valid move"""
+    st = ol.State()
+    cells = _ref_cells(name, g)
+    for i, x in enumerate(cells):
+        st.cells[i] = int(x)
+    st.player, st.turns = int(g.player), int(g.turns)
+    if name == 'br':
+        st.aux[0] = int(g._board._king_captured)
+    o = ol.OGame(gid, state=st)
+    assert (o.valid_moves() == np.asarray(g.valid_moves())).all() and (o.win_state() == np.asarray(g.win_state())).all(), name
+    return o
+
+
+def _bc_observe(nd, chosen, cpuct, fpu, cov):
+    """Node.best_child (MCTS.pyx:89-104) restated in float32 over the reference's own node state, before its choice is applied:
+    checks that the reference took the first maximum this computes, and counts ties, zero-prior picks and the seen-sum form the
+    device takes (csrc/azg_kernels.h best_child: the reduction tree for more than six visited non-zero priors within 22 binades,
+    none denormal, at most 64 children; the serial loop otherwise)"""
+    import math
+    ch = nd._children
+    with np.errstate(all='ignore'):
+        seen = 0.0
+        for c in ch:
+            if c.n > 0:
+                seen += float(c.p)
+        fpu_value = np.float32(float(np.float32(nd.v)) - float(np.float32(fpu)) * math.sqrt(float(np.float32(seen))))
+        sqn = np.float32(math.sqrt(nd.n))
+        cp = np.float32(cpuct)
+        u = np.array([(fpu_value if c.n == 0 else np.float32(c.q)) + ((cp * np.float32(c.p)) * sqn) / np.float32(1 + c.n) for c in ch], np.float32)
+    best = int(np.argmax(u))
+    assert ch[best] is chosen, 'best_child restatement disagrees with the reference'
+    cov['best_child_calls'] += 1
+    cov['tied_max'] += int((u == u[best]).sum() > 1)
+    cov['zero_prior_selected'] += int(chosen.p == 0)
+    nz = np.array([c.p for c in ch if c.n > 0 and c.p != 0], np.float32)
+    if len(nz) > 6:
+        ex = (nz.view(np.uint32) >> 23) & 0xFF
+        if len(ch) <= 64 and ex.min() > 0 and int(ex.max()) - int(ex.min()) <= 22:
+            cov['seen_sum_tree'] += 1
+        else:
+            cov['seen_sum_serial_wide'] += 1
+
+
+def gen_edge(name, seed=31, out_dir=None, verbose=True):
+    import edge_eval as ee
+    from alphazero.MCTS import MCTS
+    out_dir = out_dir or OUT
+    gid, n_random, sims, ks = EDGE_GAMES[name]
+    game_cls = _edge_game_cls(name)
+    gi = ol.game_info(gid)
+    A, NV, P = gi.action_size, gi.num_players + 1, gi.num_players
+    roots, kinds = _edge_roots(name, game_cls, gid, n_random, ks, seed)
+    R = len(roots)
+    ostates = [_root_state(name, gid, g) for g in roots]
+    out = dict(cells=np.array([o.cells() for o in ostates], np.int8), player=np.array([o.player for o in ostates], np.int32),
+               turns=np.array([o.turns for o in ostates], np.int32), aux0=np.array([o.s.aux[0] for o in ostates], np.int32),
+               root_kind=np.array(kinds, np.int32), prob_temps=np.array(EDGE_PROB_TEMPS, np.float32), sims=np.int32(sims),
+               configs=np.array([c[0] for c in EDGE_CONFIGS]))
+    KM = max(int(o.valid_moves().sum()) for o in ostates)
+    nunder = [0]
+
+    def under(*_):
+        nunder[0] += 1
+    old_call = np.seterrcall(under)
+    for (cname, fam, cpuct, fpu, nfrac, rtemp) in EDGE_CONFIGS:
+        cov = {k: 0 for k in EDGE_COV}
+        nunder[0] = 0
+        noise, temp = nfrac > 0, rtemp > 0
+        tape = rh.Tape(seed * 1000 + rh.crc(np.frombuffer(cname.encode(), np.uint8)) % 997)
+        tape.install()
+        try:
+            args = rh.ref_args(game_cls, cpuct=cpuct, fpu_reduction=fpu, root_noise_frac=nfrac if noise else 0.1,
+                               root_policy_temp=rtemp if temp else 1.1)
+            paths = []
+            depth = np.zeros((R, sims), np.int16)
+            rootn = np.zeros((R, sims, KM), np.int16); rootq = np.zeros((R, sims, KM), np.float32); rN = np.zeros((R, sims), np.int32)
+            crcs = np.zeros((R, sims), np.uint32)
+            fin = {k: [] for k in ('a', 'n', 'q', 'p', 'v', 'counts', 'probs', 'probs_raised', 'vmax', 'vavg', 'root_n', 'maxdepth', 'ctr')}
+            for r in range(R):
+                g = roots[r]
+                m = MCTS(args)
+                tape.stream = r
+                for s in range(sims):
+                    leaf = m.find_leaf(g)
+                    pn = list(m._path)
+                    for i, nd in enumerate(pn):
+                        _bc_observe(nd, pn[i + 1] if i + 1 < len(pn) else m._curnode, cpuct, fpu, cov)
+                    acts = [n.a for n in pn[1:]] + ([m._curnode.a] if pn else [])
+                    depth[r, s] = m.depth
+                    assert len(acts) == m.depth
+                    paths.append(acts)
+                    term = np.asarray(leaf.win_state()).any()
+                    p, v = ee.row(fam, tape.seed, r, s, A, NV, None if term else np.asarray(leaf.valid_moves()))
+                    crcs[r, s] = ee.row_crc(p, v)
+                    val = np.asarray(m._curnode.e, np.float32) if m._curnode.e.any() else v
+                    for nd in pn:                                   # _get_value (:291-295) of every backup step
+                        gv = np.float32(val[nd.player] + val[P] / np.float32(P)) if len(val) > P else val[nd.player]
+                        cov['draw_backups'] += int(gv == np.float32(0.5))
+                    with np.errstate(under='call'):                 # (see DESIGN.md section 7: the reference raises here)
+                        m.process_results(leaf, v, p, noise, temp)
+                    ch = m._root._children
+                    rootn[r, s, :len(ch)] = [c.n for c in ch]; rootq[r, s, :len(ch)] = [c.q for c in ch]
+                    rN[r, s] = m._root.n
+                ch = m._root._children
+                pad = KM - len(ch)
+                fin['a'].append(np.array([c.a for c in ch] + [-1] * pad, np.int16))
+                fin['n'].append(np.array([c.n for c in ch] + [0] * pad, np.int32))
+                for f in ('q', 'p', 'v'):
+                    fin[f].append(np.array([getattr(c, f) for c in ch] + [0] * pad, np.float32))
+                fin['counts'].append(np.asarray(m.counts(g)).astype(np.int32))
+                pr, raised = [], []
+                for t in EDGE_PROB_TEMPS:                       # under the reference's own np.seterr(all='raise')
+                    try:
+                        pr.append(np.asarray(m.probs(g, t), np.float32)); raised.append(0)
+                    except FloatingPointError:
+                        pr.append(np.full(A, np.nan, np.float32)); raised.append(1)
+                fin['probs'].append(np.array(pr)); fin['probs_raised'].append(raised)
+                fin['vmax'].append(m.value(False)); fin['vavg'].append(m.value(True))
+                fin['root_n'].append(m._root.n); fin['maxdepth'].append(m.max_depth)
+                fin['ctr'].append(tape.ctr[r])
+        finally:
+            tape.uninstall()
+        L = max(max(len(x) for x in paths), 1)
+        pa = np.full((R * sims, L), -1, np.int16)
+        for i, x in enumerate(paths):
+            pa[i, :len(x)] = x
+        cov['underflows'] = nunder[0]
+        if fam != 'spread':
+            assert nunder[0] == 0, (name, cname)                # only the spread rows underflow
+        pre = cname + '_'
+        out[pre + 'seed'] = np.uint64(tape.seed)
+        out[pre + 'cfg'] = np.array([cpuct, fpu, nfrac, rtemp, sims], np.float64)
+        out[pre + 'family'] = np.array(fam)
+        out[pre + 'paths'] = pa.reshape(R, sims, L); out[pre + 'depth'] = depth
+        out[pre + 'rootn'] = rootn; out[pre + 'rootq'] = rootq; out[pre + 'rootN'] = rN; out[pre + 'row_crc'] = crcs
+        for k, v in fin.items():
+            out[pre + k] = np.array(v)
+        out[pre + 'cov'] = np.array([cov[k] for k in EDGE_COV], np.int64)
+        if verbose:
+            print('  %s_edge/%s: max depth %d, %s' % (name, cname, int(depth.max()), cov))
+    np.seterrcall(old_call)
+    out['cov_names'] = np.array(EDGE_COV)
+    tot = sum(out[c[0] + '_cov'] for c in EDGE_CONFIGS)
+    for k, floor in EDGE_FLOORS.items():
+        assert tot[EDGE_COV.index(k)] >= floor, (name, k, int(tot[EDGE_COV.index(k)]), floor)
+    # the agent: uniform priors, draw-heavy values, temperature 0 from the first move (np.argmax ties in the counts), symmetric samples
+    o, _ = run_ref_agent(game_cls, gid, 'edge_agent', 6 if name != 'br' else 4, 12, 6 if name != 'br' else 3,
+                         dict(startTemp=0, temp_scaling_fn=_zero_temp), seed + 5, evaluator=ee.agent_row)
+    for k, v in o.items():
+        out['agent_' + k] = v
+    out['agent_slot_base'] = np.int32(0)
+    np.savez_compressed(os.path.join(out_dir, name + '_edge.npz'), **out)
+    if verbose:
+        print('%s_edge: %d roots (k = %s), %d configs; agent %d rounds, %d samples; coverage %s'
+              % (name, R, sorted(int(o.valid_moves().sum()) for o in ostates), len(EDGE_CONFIGS), len(o['actions']), len(o['s_pi']),
+                 dict(zip(EDGE_COV, tot.tolist()))))
+
+
+def _zero_temp(cur_temp, turns, const_max_turns):
+    return 0
+
+
 def main():
     which = sys.argv[1:] or ['c4_rules', 'c4_tree', 'c4_agent', 'c4_arena']
     rh.import_reference()
@@ -623,6 +888,9 @@ def main():
         gen_agent(TM, ol.GAME_TRIMOK, 'tm', seed=777,
                   configs=[('plain', 8, 15, 12, dict()), ('noisy', 6, 10, 8, dict(add_root_noise=True, add_root_temp=True)),
                            ('wide', 32, 50, 40, dict())])
+    for name in ('c4', 'tm', 'br'):
+        if name + '_edge' in which or 'edge' in which:
+            gen_edge(name)
     if 'br_agent' in which:
         gen_agent(br_game_cls(), ol.GAME_BRANDUBH, 'br', seed=321,
                   configs=[('plain', 6, 12, 4, dict()), ('noisy', 4, 10, 3, dict(add_root_noise=True, add_root_temp=True)),

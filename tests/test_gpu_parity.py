@@ -69,7 +69,7 @@ def test_c4_tree_vs_reference_goldens(torch_mod, cname):
     obs = eng.new_obs()
     for s in range(sims):
         eng.select(obs)
-        for r in range(0, R, 7):                      # spot-check leaf paths every sim on a subset of roots
+        for r in range(0, R, 7):                      # spot-check leaf paths every sim on a subset of roots (every root: tests/test_gpu_tree_edges.py)
             path = eng.last_path(r)
             assert len(path) == d[cname + '_depth'][r, s]
             assert (path[:24] == d[cname + '_paths'][r, s][:len(path)]).all(), (r, s)

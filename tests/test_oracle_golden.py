@@ -312,7 +312,7 @@ AGENT_CFGS = {
 }
 
 
-def run_oracle_agent(game, d, cname, kw):
+def run_oracle_agent(game, d, cname, kw, evaluator=ol.fake_eval):
     gi = ol.game_info(game)
     A, NV = gi.action_size, gi.num_players + 1
     B, sims, games = int(d[cname + '_B']), int(d[cname + '_sims']), int(d[cname + '_games'])
@@ -329,7 +329,7 @@ def run_oracle_agent(game, d, cname, kw):
             if not kw.get('is_warmup'):
                 rec['obs_crc'].append([crc(obs[i]) for i in range(B)])
                 for row in range(B):
-                    pol[row], val[row] = ol.fake_eval(seed, slot_base + rg[row], step, A, NV)
+                    pol[row], val[row] = evaluator(seed, slot_base + rg[row], step, A, NV)
             ag.process_batch(pol, val)
             step += 1
         cts = []
@@ -601,3 +601,138 @@ def test_tm_agent_vs_reference(cname, kw):
     assert (obs == d[cname + '_s_obs']).all() and (pi == d[cname + '_s_pi']).all() and (z == d[cname + '_s_z']).all()
     ws, turns, slot = ag.results()
     assert (ws == d[cname + '_r_ws']).all() and (turns == d[cname + '_r_turns']).all()
+
+
+# ------------------------------------------------------------------------------------------------ edge family
+# tests/golden/{c4,tm,br}_edge.npz: the reference itself at PUCT ties, zero and denormal priors, exact draw values, cpuct 0 / 50,
+# fpu_reduction -1 / 0, noise_frac 1, root temperatures 0.5 / 2 / 1.1 and roots with 1, 2, 63, 64, 65 children (make_goldens.py
+# gen_edge, rows from tests/edge_eval.py).  tests/test_gpu_tree_edges.py holds the device to the same fixtures.
+import edge_eval as ee  # noqa: E402
+
+EDGE_FLOORS = {'tied_max': 500, 'zero_prior_selected': 50, 'seen_sum_tree': 100, 'seen_sum_serial_wide': 50, 'draw_backups': 100}
+EDGE_CASES = [(n, c) for n in ('c4', 'tm', 'br') for c in ee.CONFIGS]
+
+
+def _edge(name):
+    return dict(np.load(os.path.join(G, name + '_edge.npz')))
+
+
+def check_edge_probs(pr, d, cname, r, ti, t):
+    """one probs row against the fixture: exact at T in {1, 2, 0.5, 0}, the powf tier otherwise; where the reference raised
+    FloatingPointError (an underflow under its np.seterr(all='raise')), the untrapped value of the same expression"""
+    ref = d[cname + '_probs'][r][ti]
+    if d[cname + '_probs_raised'][r][ti]:
+        ref = ee.probs_untrapped(d[cname + '_counts'][r], t)
+        assert np.allclose(pr, ref, rtol=3e-7, atol=1e-12, equal_nan=True), (r, t)
+    elif t in (1.0, 2.0, 0.5, 0.0):
+        assert (pr == ref).all(), (r, t)
+    else:
+        assert np.allclose(pr, ref, rtol=3e-7, atol=1e-12), (r, t)
+
+
+@pytest.mark.parametrize('name', ['c4', 'tm', 'br'])
+def test_edge_fixture_reaches_its_edges(name):
+    """the coverage the generator counted on the reference's own trees, over all configs of a game, and the root sizes"""
+    d = _edge(name)
+    assert list(d['configs']) == ee.CONFIGS
+    names = list(d['cov_names'])
+    tot = sum(d[c + '_cov'] for c in ee.CONFIGS)
+    for k, floor in EDGE_FLOORS.items():
+        assert tot[names.index(k)] >= floor, (k, tot[names.index(k)])
+    ks = set(int(g.valid_moves().sum()) for g in ee.roots(d, ee.GAMES[name]))
+    assert ks >= ({63, 64, 65} if name == 'br' else {1, 2})
+    if name != 'tm':                                       # (a trimok game lasts at most 25 moves)
+        assert max(int(d[c + '_depth'].max()) for c in ee.CONFIGS) >= 24                      # paths of 24 and more actions
+        assert sum(int(d[c + '_cov'][names.index('underflows')]) for c in ee.CONFIGS) > 0   # (the spread rows reach the reference's trap)
+    assert sum(int(d[c + '_probs_raised'].sum()) for c in ee.CONFIGS) > 0
+    tied0 = sum(int(((d[c + '_counts'] == d[c + '_counts'].max(1, keepdims=True)).sum(1) > 1).sum()) for c in ee.CONFIGS)
+    assert tied0 > 0                                                                          # argmax ties at temperature 0
+
+
+@pytest.mark.parametrize('name,cname', EDGE_CASES)
+def test_edge_tree_vs_reference(name, cname):
+    d = _edge(name)
+    gid = ee.GAMES[name]
+    gi = ol.game_info(gid)
+    A, NV = gi.action_size, gi.num_players + 1
+    cpuct, fpu, nfrac, rtemp, sims = d[cname + '_cfg']
+    noise, temp, sims = nfrac > 0, rtemp > 0, int(sims)
+    fam, seed = str(d[cname + '_family']), int(d[cname + '_seed'])
+    exact = not temp or rtemp in (2.0, 0.5)            # ** 0.5 and ** 2 are numpy's exact fast paths; 1.1 is the powf tier
+    roots = ee.roots(d, gid)
+    for r, g in enumerate(roots):
+        m = ol.OMCTS(gid, cpuct=cpuct, fpu_reduction=fpu, root_noise_frac=nfrac if noise else 0.1,
+                     root_policy_temp=rtemp if temp else 1.1, seed=seed, stream=r)
+        for s in range(sims):
+            m.find_leaf(g)
+            path = m.last_path()
+            dep = int(d[cname + '_depth'][r, s])
+            assert len(path) == dep and (path == d[cname + '_paths'][r, s][:dep]).all(), (r, s)
+            p, v = ee.leaf_row(fam, seed, g, r, s, path, A, NV)
+            assert ee.row_crc(p, v) == d[cname + '_row_crc'][r, s], (r, s)
+            m.process_results(v, p, noise, temp)
+            ch = m.root_children()
+            k = len(ch['a'])
+            assert (ch['n'] == d[cname + '_rootn'][r, s][:k]).all() and m.root_n == d[cname + '_rootN'][r, s], (r, s)
+            if exact:
+                assert (ch['q'] == d[cname + '_rootq'][r, s][:k]).all(), (r, s)
+            else:
+                assert np.allclose(ch['q'], d[cname + '_rootq'][r, s][:k], atol=1e-5), (r, s)
+        ch = m.root_children()
+        k = len(ch['a'])
+        assert (ch['a'] == d[cname + '_a'][r][:k]).all() and (d[cname + '_a'][r][k:] == -1).all()
+        assert (ch['n'] == d[cname + '_n'][r][:k]).all()
+        for f in ('q', 'p', 'v'):
+            if exact:
+                assert (ch[f] == d[cname + '_' + f][r][:k]).all(), (f, r)
+            else:
+                assert np.allclose(ch[f], d[cname + '_' + f][r][:k], atol=1e-5), (f, r)
+        assert (m.counts() == d[cname + '_counts'][r]).all()
+        for ti, t in enumerate(d['prob_temps']):
+            check_edge_probs(m.probs(float(t)), d, cname, r, ti, float(t))
+        assert m.value(False) == d[cname + '_vmax'][r] and m.value(True) == d[cname + '_vavg'][r]
+        assert m.root_n == d[cname + '_root_n'][r] and m.max_depth == d[cname + '_maxdepth'][r]
+        assert ol.lib().azo_mcts_tape_ctr(m.h) == d[cname + '_ctr'][r]
+
+
+def _zero_temp(cur_temp, turns, const_max_turns):
+    return 0
+
+
+@pytest.mark.parametrize('name', ['c4', 'tm', 'br'])
+def test_edge_agent_vs_reference(name):
+    """uniform priors, draw-heavy values, temperature 0 from the first move: every move is np.argmax over visit counts that tie"""
+    d = _edge(name)
+    gid = ee.GAMES[name]
+    ag, rec = run_oracle_agent(gid, d, 'agent', dict(start_temp=0.0, temp_fn=_zero_temp), evaluator=ee.agent_row)
+    assert (np.array(rec['sims']) == d['agent_round_sims']).all()
+    assert (np.array(rec['counts']) == d['agent_counts']).all()
+    assert (np.array(rec['actions']) == d['agent_actions']).all()
+    assert (np.array(rec['games_played']) == d['agent_games_played']).all()
+    assert (np.array(rec['obs_crc'], np.uint32) == d['agent_obs_crc']).all()
+    obs, pi, z = ag.samples()
+    assert obs.shape == d['agent_s_obs'].shape and len(obs) > 0
+    assert (obs == d['agent_s_obs']).all() and (pi == d['agent_s_pi']).all() and (z == d['agent_s_z']).all()
+    ws, turns, slot = ag.results()
+    assert (ws == d['agent_r_ws']).all() and (turns == d['agent_r_turns']).all()
+
+
+REF = '/root/reference'
+
+
+@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'alphazero')), reason='needs the reference checkout (build container only)')
+def test_edge_fixtures_regenerate_identically(tmp_path):
+    """make_goldens.py gen_edge, run on the reference again into a temporary directory, writes the committed fixtures array for array"""
+    import subprocess
+    import sys
+    code = ('import sys; sys.path.insert(0, %r); import make_goldens as mg; mg.rh.import_reference()\n'
+            'for n in ("c4", "tm", "br"): mg.gen_edge(n, out_dir=%r, verbose=False)') % (G, str(tmp_path))
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
+    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=1800, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    for n in ('c4', 'tm', 'br'):
+        new, old = np.load(os.path.join(str(tmp_path), n + '_edge.npz')), np.load(os.path.join(G, n + '_edge.npz'))
+        assert sorted(new.files) == sorted(old.files), n
+        for k in old.files:
+            a, b = new[k], old[k]
+            assert a.dtype == b.dtype and a.shape == b.shape and (a.tobytes() == b.tobytes()), (n, k)
