@@ -30,6 +30,8 @@ def encode_state(gs):
         return np.asarray(gs._board.pieces, np.int8).reshape(-1), gs.player, gs.turns
     if gid == 1:                   # the reference's own brandubh Game (envs/brandubh/fastafl.pyx:121-131; fastafl/cengine.pyx:24-32,59)
         return np.asarray(gs._board._state, np.int8).reshape(-1), gs.player, gs.turns, int(gs._board._king_captured)
+    if gid == 3:                   # the reference's own othello Game (envs/othello/othello.pyx:17-41): pieces[x][y] -> cells[8x + y]
+        return np.asarray(gs._board.pieces, np.int8).reshape(-1), gs.player, gs.turns
     raise NotImplementedError('cannot encode %r for the device engine' % type(gs))
 
 

@@ -653,8 +653,8 @@ template <class SEARCH> constexpr int tower_min_blocks() { if constexpr (__is_sa
 // cg, pixel group ph, k group kg), every wave runs 9 k-steps over ALL its pixel group's subtiles and finishes half of them: the
 // partial sums of the other half go to the partner through LDS.  No weight fragment is fetched twice (unlike a pixel split), every
 // SIMD gets a wave of each of the CU's two workgroups, and a wave's load issue hides under the other's MFMAs.
-// KHALF order (7x7 x 64 channels, every tile shape): out = (bias + sum over the first channel half) + (sum over the second half).
-template <int H, int W, int C> constexpr bool tower_khalf_order() { return H == 7 && W == 7 && C == 64; }
+// KHALF order (7x7 and 8x8 x 64 channels, every tile shape): out = (bias + sum over the first channel half) + (sum over the second half).
+template <int H, int W, int C> constexpr bool tower_khalf_order() { return ((H == 7 && W == 7) || (H == 8 && W == 8)) && C == 64; }
 // One-board tiles keep the layers' biases and the blocks' pre-activation affines in LDS (behind everything else): a tile with one wave
 // per SIMD has nothing to cover the L2 round trip of a parameter fetch (~270 cycles, in every layer, and the persistent launches would
 // repeat it in every simulation).  fp32 biases [2 * nblocks + 1][C], then the affine as the fp16 values the epilogue uses, scale

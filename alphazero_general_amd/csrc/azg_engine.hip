@@ -48,8 +48,9 @@ static const azg_game_info k_info[] = {
     {C4::A, C4::OBS_C, C4::H, C4::W, C4::P, C4::HAS_DRAW, C4::MAX_TURNS, C4::NSYM, C4::CELLS, C4::MAXK},
     {BR::A, BR::OBS_C, BR::H, BR::W, BR::P, BR::HAS_DRAW, BR::MAX_TURNS, BR::NSYM, BR::CELLS, BR::MAXK},
     {TM::A, TM::OBS_C, TM::H, TM::W, TM::P, TM::HAS_DRAW, TM::MAX_TURNS, TM::NSYM, TM::CELLS, TM::MAXK},
+    {OT::A, OT::OBS_C, OT::H, OT::W, OT::P, OT::HAS_DRAW, OT::MAX_TURNS, OT::NSYM, OT::CELLS, OT::MAXK},
 };
-static const int k_num_games = 3;
+static const int k_num_games = 4;
 
 extern "C" int azg_abi_version(void) { return AZG_ABI_VERSION; }
 #ifndef AZG_SRC_SHA
@@ -94,6 +95,7 @@ template <typename T> static int dalloc(azg_engine *e, T **p, size_t count) {
     case AZG_GAME_CONNECT4: { using G = C4; CALL; } break; \
     case AZG_GAME_BRANDUBH: { using G = BR; CALL; } break; \
     case AZG_GAME_TRIMOK: { using G = TM; CALL; } break; \
+    case AZG_GAME_OTHELLO: { using G = OT; CALL; } break; \
     default: return fail(AZG_E_UNSUPPORTED, "game has no device rules"); }
 
 static void prof_begin(azg_engine *e, hipStream_t s, int fam, EvPair &p) {
@@ -998,7 +1000,21 @@ static int dispatch_tower(hipStream_t s, int game, int channels, const TowerPara
         if (bt == 2) return launch_tower<TM::H, TM::W, 2, 32>(s, P);
         return launch_tower<TM::H, TM::W, 5, 32>(s, P);
     }
-    return fail(AZG_E_UNSUPPORTED, "no MFMA tower for this game / channel count (supported: connect4 x {32,64,128}, brandubh x {64,128}, trimok x 32 channels)");
+    // othello: an 8x8 board is exactly four pixel subtiles, so no tile carries pad rows; the tiles of the widths it shares with connect4's
+    // default net (32) and brandubh's (64)
+    if (game == AZG_GAME_OTHELLO && channels == 32) {            // one cout group, the tile's pixel subtiles dealt to two waves
+        const int bt = forced ? forced : n <= 4 * cus ? 2 : 4;
+        if (bt == 2) return launch_tower<OT::H, OT::W, 2, 32, 2>(s, P);
+        return launch_tower<OT::H, OT::W, 4, 32, 2>(s, P);
+    }
+    if (game == AZG_GAME_OTHELLO && channels == 64) {            // two cout groups: the k-split 1-board tile at small batches, as brandubh
+        const int bt = forced ? forced : n <= 2 * cus ? 1 : 2;
+        const int sp = psplit ? psplit : n <= 2 * cus ? 3 : n <= 4 * cus ? 2 : 1;
+        if (bt == 1) return launch_tower<OT::H, OT::W, 1, 64, 1, NoSearch, 2>(s, P);
+        if (sp == 2) return launch_tower<OT::H, OT::W, 2, 64, 2>(s, P);
+        return launch_tower<OT::H, OT::W, 2, 64>(s, P);
+    }
+    return fail(AZG_E_UNSUPPORTED, "no MFMA tower for this game / channel count (supported: connect4 x {32,64,128}, brandubh x {64,128}, trimok x 32, othello x {32,64} channels)");
 }
 
 // [boards, C, H*W] f32 planes (what GameState.observation / the reference's batch tensors hold) -> the tower's input rows [boards * H*W][8] fp16
@@ -1165,13 +1181,25 @@ static int wide_tile_launch(azg_engine *e, hipStream_t s, const TowerParams &P, 
     } else if (game == AZG_GAME_CONNECT4 && channels == 64) {
         if (bt == 1) return launch_tower<C4::H, C4::W, 1, 64, 2, SearchWide<C4, 2, EXACT>>(s, P, SearchWide<C4, 2, EXACT>{e->v, sims, hd, hf}, init, occ);   // four wavefronts per game
         if (bt == 2) return launch_tower<C4::H, C4::W, 2, 64, 2, SearchWide<C4, 2, EXACT>>(s, P, SearchWide<C4, 2, EXACT>{e->v, sims, hd, hf}, init, occ);   // walker + helper per game
+    } else if (game == AZG_GAME_OTHELLO && channels == 32) {
+        // the default net of an unconfigured Coach (32 x 4): connect4-32's shapes
+        if (bt == 1) return launch_tower<OT::H, OT::W, 1, 32, 2, SearchWide<OT, 1, EXACT>>(s, P, SearchWide<OT, 1, EXACT>{e->v, sims, hd, hf}, init, occ);
+        if (bt == 2) return launch_tower<OT::H, OT::W, 2, 32, 4, SearchWide<OT, 2, EXACT>>(s, P, SearchWide<OT, 2, EXACT>{e->v, sims, hd, hf}, init, occ);   // walker + helper per game
+    } else if (game == AZG_GAME_OTHELLO && channels == 64) {
+        // envs/othello/train.py's net (64 x 4, 16 + 16 head channels): brandubh-64's shapes, two workgroups of four wavefronts per CU
+        using SW = SearchWide<OT, 2, EXACT>;
+        const SW sa{e->v, sims, hd, hf};
+        if (bt == 1) return launch_tower<OT::H, OT::W, 1, 64, 1, SW, 2>(s, P, sa, init, occ);      // k-split tower
+        if (bt == 2) return launch_tower<OT::H, OT::W, 2, 64, 2, SW>(s, P, sa, init, occ);
+        if (bt == 3) return launch_tower<OT::H, OT::W, 3, 64, 2, SW>(s, P, sa, init, occ);
+        if (bt == 4) return launch_tower<OT::H, OT::W, 4, 64, 2, SW>(s, P, sa, init, occ);
     }
     return AZG_E_UNSUPPORTED;
 }
 
 static int wide_max_tile(int game, int channels) {
-    if (game == AZG_GAME_BRANDUBH && channels == 64) return 4;
-    if ((game == AZG_GAME_TRIMOK && channels == 32) || (game == AZG_GAME_CONNECT4 && (channels == 32 || channels == 64))) return 2;
+    if ((game == AZG_GAME_BRANDUBH || game == AZG_GAME_OTHELLO) && channels == 64) return 4;
+    if ((game == AZG_GAME_TRIMOK && channels == 32) || (game == AZG_GAME_CONNECT4 && (channels == 32 || channels == 64)) || (game == AZG_GAME_OTHELLO && channels == 32)) return 2;
     return 0;
 }
 
@@ -1186,6 +1214,7 @@ template <bool EXACT>
 static int wide_tile_model(azg_engine *e, int channels, int nblocks, int cus, const int *occ) {
     const int game = e->cfg.game, B = e->v.B, tmax = wide_max_tile(game, channels);
     if (game != AZG_GAME_BRANDUBH) {
+        // (othello has no phase budget of its own yet: this prior, and the set-up trial of every tile, decide)
         // one game per workgroup up to two games per CU (3-player env, M expansions/s at 256 / 512 / 1024 games on 256 CUs: one game per
         // workgroup 20.7 / 37.4 / 39.4, two 16.3 / 31.3 / 48.0: profiles/r05_wide_tile_sweep.txt); beyond that the shared weight stream wins
         return (occ[0] > 0 && B <= 2 * cus) || tmax < 2 || occ[1] <= 0 ? 1 : 2;
@@ -1320,7 +1349,7 @@ static int search_wide(azg_engine *e, void *stream, const void *w, const float *
     const int A = e->gi.action_size, NV = e->gi.num_players + 1, hw = e->gi.obs_h * e->gi.obs_w;
     if (feat_k != (hw * 16 + 31) / 32 * 32) return fail(AZG_E_INVALID_ARG, "feat_k must be H*W*16 rounded up to 32");
     if (wide_max_tile(e->cfg.game, channels) == 0)
-        return fail(AZG_E_UNSUPPORTED, "persistent wide-head search: brandubh x 64, the 3-player env x 32 and connect4 x {32, 64} channels (use azg_select / network / azg_backup)");
+        return fail(AZG_E_UNSUPPORTED, "persistent wide-head search: brandubh x 64, the 3-player env x 32, connect4 x {32, 64} and othello x {32, 64} channels (use azg_select / network / azg_backup)");
     TowerParams P{nullptr, w, bias, pre_scale, pre_shift, nullptr, e->v.B, nblocks, nullptr, nullptr, nullptr, nullptr, A, NV, nullptr, head1_w, head1_b, nullptr, feat_k,
                   nullptr, 0, {}};
     hipStream_t s = (hipStream_t)stream;
@@ -1441,6 +1470,7 @@ extern "C" int azg_tower_layout(int game, int boards_per_tile, int channels, int
     AZG_LAYOUT(C4, 1, 128); AZG_LAYOUT(C4, 2, 128); AZG_LAYOUT(C4, 4, 128); AZG_LAYOUT(C4, 4, 64); AZG_LAYOUT(C4, 2, 32); AZG_LAYOUT(C4, 4, 32);
     AZG_LAYOUT(BR, 1, 64); AZG_LAYOUT(BR, 2, 64); AZG_LAYOUT(BR, 2, 128);
     AZG_LAYOUT(TM, 2, 32); AZG_LAYOUT(TM, 5, 32);
+    AZG_LAYOUT(OT, 1, 32); AZG_LAYOUT(OT, 2, 32); AZG_LAYOUT(OT, 4, 32); AZG_LAYOUT(OT, 1, 64); AZG_LAYOUT(OT, 2, 64); AZG_LAYOUT(OT, 3, 64); AZG_LAYOUT(OT, 4, 64);
 #undef AZG_LAYOUT
     return fail(AZG_E_UNSUPPORTED, "no tower instantiation for this (game, boards per tile, channels)");
 }

@@ -20,6 +20,7 @@ struct C4 {
     static constexpr int ID = AZG_GAME_CONNECT4;
     static constexpr int A = 7, H = 6, W = 7, CELLS = 42, P = 2, HAS_DRAW = 1, MAX_TURNS = 42, NSYM = 2;
     static constexpr int OBS_C = 4, OBS = OBS_C * CELLS, MAXK = 7;
+    static constexpr int SYM_RAW = 0;                                    // symmetries()[SYM_RAW] is the position itself
     struct S { uint64_t b0, b1; int player, turns; };
 
     static AZG_DEV S load(const azg_state *st, int lane) {
@@ -127,6 +128,7 @@ struct BR {
     static constexpr int ID = AZG_GAME_BRANDUBH;
     static constexpr int A = 588, H = 7, W = 7, CELLS = 49, P = 2, HAS_DRAW = 1, MAX_TURNS = 100, NSYM = 8;
     static constexpr int OBS_C = 5, OBS = OBS_C * CELLS, MAXK = 96;      // 8 attackers x 12 destinations bounds the move list
+    static constexpr int SYM_RAW = 0;
     static constexpr uint64_t ALL = (1ULL << 49) - 1;
     static constexpr uint64_t COL0 = 0x0040810204081ULL, COL6 = COL0 << 6;
     struct S { int cell; int player, turns, kc; };
@@ -354,6 +356,7 @@ struct TM {
     static constexpr int ID = AZG_GAME_TRIMOK;
     static constexpr int A = 25, H = 5, W = 5, CELLS = 25, P = 3, HAS_DRAW = 1, MAX_TURNS = 25, NSYM = 1;
     static constexpr int OBS_C = 5, OBS = OBS_C * CELLS, MAXK = 25;
+    static constexpr int SYM_RAW = 0;
     struct S { uint32_t b[3]; int player, turns; };
     static AZG_DEV S load(const azg_state *st, int lane) {
         const int8_t v = lane < CELLS ? st->cells[lane] : (int8_t)0;
@@ -423,6 +426,129 @@ struct TM {
     }
     static AZG_DEV S symmetry(const S &s, int k) { (void)k; return s; }
     static AZG_DEV int sym_action(int a, int k) { (void)k; return a; }
+};
+
+
+// ================================================================================================ othello
+// alphazero/envs/othello/othello.pyx + OthelloLogic.pyx.  Cell i = 8x + y of the reference's pieces[x][y] (action a = 8x + y places a
+// stone on cell a), colour 1 for player 0 and -1 for player 1.  The board is two 64-bit bitboards in SGPRs: every bit is a cell, so
+// there is no padding bit, and a shift that moves along y must clear the column it would wrap out of first.  No pass action: the game
+// ends as soon as the player to move has no legal move (win_state, othello.pyx:83-96), scored by the disc difference from the mover.
+struct OT {
+    static constexpr int ID = AZG_GAME_OTHELLO;
+    static constexpr int A = 64, H = 8, W = 8, CELLS = 64, P = 2, HAS_DRAW = 1, MAX_TURNS = 64, NSYM = 8;
+    static constexpr int OBS_C = 1, OBS = OBS_C * CELLS, MAXK = 60;      // at most 60 empty squares: one wavefront holds the move list
+    static constexpr int SYM_RAW = 7;                                    // the identity is the LAST entry of symmetries() (k = 2*(4-1) + 1)
+    static constexpr uint64_t COL0 = 0x0101010101010101ULL, COL7 = 0x8080808080808080ULL;
+    struct S { uint64_t b0, b1; int player, turns; };                    // b0: colour 1 (player 0), b1: colour -1
+
+    // one step of the 8 directions (OthelloLogic.pyx:24); d = 0..7, x = bit >> 3, y = bit & 7
+    static AZG_DEV uint64_t step(uint64_t m, int d) {
+        switch (d) {
+        case 0: return (m & ~COL7) << 9;     // (+1, +1)
+        case 1: return m << 8;               // (+1,  0)
+        case 2: return (m & ~COL0) << 7;     // (+1, -1)
+        case 3: return (m & ~COL0) >> 1;     // ( 0, -1)
+        case 4: return (m & ~COL0) >> 9;     // (-1, -1)
+        case 5: return m >> 8;               // (-1,  0)
+        case 6: return (m & ~COL7) >> 7;     // (-1, +1)
+        default: return (m & ~COL7) << 1;    // ( 0, +1)
+        }
+    }
+    static AZG_DEV S load(const azg_state *st, int lane) {
+        const int8_t v = st->cells[lane];
+        S s;
+        s.b0 = __ballot(v == 1);
+        s.b1 = __ballot(v == -1);
+        s.player = __builtin_amdgcn_readfirstlane(st->player);
+        s.turns = __builtin_amdgcn_readfirstlane(st->turns);
+        return s;
+    }
+    static AZG_DEV void init(S &s) {                                     // OthelloLogic.pyx Board.__init__: pieces[3][4] = pieces[4][3] = 1, [3][3] = [4][4] = -1
+        s.b0 = (1ULL << 28) | (1ULL << 35); s.b1 = (1ULL << 27) | (1ULL << 36); s.player = 0; s.turns = 0;
+    }
+    static AZG_DEV int cell(const S &s, int i) { return (int)((s.b0 >> i) & 1) - (int)((s.b1 >> i) & 1); }
+    static AZG_DEV void store(const S &s, azg_state *st, int lane) {
+        st->cells[lane] = (int8_t)cell(s, lane);
+        if (lane == 0) { st->player = s.player; st->turns = s.turns; st->aux[0] = 0; st->aux[1] = 0; }
+    }
+    // empty squares that close a run of the opponent's stones against one of `own` (get_legal_moves, OthelloLogic.pyx:67-78):
+    // directional fills, a run is at most 6 stones long
+    static AZG_DEV uint64_t moves(uint64_t own, uint64_t opp) {
+        const uint64_t empty = ~(own | opp);
+        uint64_t mv = 0;
+#pragma unroll
+        for (int d = 0; d < 8; d++) {
+            uint64_t t = step(own, d) & opp;
+#pragma unroll
+            for (int i = 0; i < 5; i++) t |= step(t, d) & opp;
+            mv |= step(t, d) & empty;
+        }
+        return mv;
+    }
+    static AZG_DEV uint64_t valid_mask(const S &s) { return s.player == 0 ? moves(s.b0, s.b1) : moves(s.b1, s.b0); }
+    // execute_move (OthelloLogic.pyx:121-142, _get_flips :162-176): in each direction, the run of opponent stones the move closes
+    static AZG_DEV void play(S &s, int a) {
+        a = __builtin_amdgcn_readfirstlane(a) & 63;
+        const uint64_t m = 1ULL << a;
+        uint64_t own = s.player == 0 ? s.b0 : s.b1, opp = s.player == 0 ? s.b1 : s.b0;
+        uint64_t flips = 0;
+#pragma unroll
+        for (int d = 0; d < 8; d++) {
+            uint64_t run = 0, x = step(m, d);
+            while (x & opp) { run |= x; x = step(x, d); }
+            if (x & own) flips |= run;
+        }
+        own |= flips | m; opp &= ~flips;
+        if (s.player == 0) { s.b0 = own; s.b1 = opp; } else { s.b0 = opp; s.b1 = own; }
+        s.player ^= 1; s.turns += 1;
+    }
+    // win_state (othello.pyx:83-96): the player to move has no legal move -> count_diff from the mover's colour decides
+    static AZG_DEV int win_bits(const S &s) {
+        if (valid_mask(s) != 0) return 0;
+        const int own = __popcll(s.player == 0 ? s.b0 : s.b1), opp = __popcll(s.player == 0 ? s.b1 : s.b0);
+        return own > opp ? 1 << s.player : own < opp ? 1 << (s.player ^ 1) : 4;
+    }
+    // lane i < k receives the i-th legal move in ascending order: the lane of a legal square pushes its index to the lane of its rank
+    // (the legal squares below it: mbcnt), one ds_permute; the others push to lane 63, which nobody reads (k <= 60)
+    static AZG_DEV int valid_list(const S &s, int lane, int *act_lds, int (&my_a)[1]) {
+        const uint64_t vm = valid_mask(s);
+        const int k = __popcll(vm);
+        const bool legal = ((vm >> lane) & 1) != 0;
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(vm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)vm, 0u));
+        const int a = __builtin_amdgcn_ds_permute((legal ? rank : 63) << 2, lane);
+        my_a[0] = lane < k ? a : -1; (void)act_lds;
+        return k;
+    }
+    // observation (othello.pyx:98-99): one plane of the raw pieces, absolute colours
+    template <typename OT_> static AZG_DEV void write_obs(const S &s, OT_ *out, int lane) { out[lane] = (OT_)(float)cell(s, lane); }
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    static AZG_DEV h8 obs8(const S &s, int lane) {
+        return (h8){(_Float16)(float)cell(s, lane), (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+    }
+    static AZG_DEV void write_obs_nhwc8(const S &s, _Float16 *out, int lane) { *reinterpret_cast<h8 *>(out + lane * 8) = obs8(s, lane); }
+    // symmetries (othello.pyx:101-120): entry k = 2(i-1) + (0 if flipped else 1), i = 1..4: fliplr^flip(rot90^i(pieces)), so k = 7 is the
+    // identity.  np.rot90: out[r][c] = in[c][7-r]; np.fliplr: out[r][c] = in[r][7-c]
+    static AZG_DEV S symmetry(const S &s, int k) {
+        const int lane = threadIdx.x & 63;
+        const int i = k / 2 + 1;
+        int r = lane >> 3, c = lane & 7;
+        if ((k & 1) == 0) c = 7 - c;
+        for (int t = 0; t < i; t++) { const int nr = c, nc = 7 - r; r = nr; c = nc; }
+        const int src = r * 8 + c;
+        S o = s;
+        o.b0 = __ballot((s.b0 >> src) & 1);
+        o.b1 = __ballot((s.b1 >> src) & 1);
+        return o;
+    }
+    // where pi[a] lands under symmetry k (the forward maps: rot90 sends (r, c) to (7-c, r), fliplr (r, c) to (r, 7-c))
+    static AZG_DEV int sym_action(int a, int k) {
+        const int i = k / 2 + 1;
+        int r = a >> 3, c = a & 7;
+        for (int t = 0; t < i; t++) { const int nr = 7 - c, nc = r; r = nr; c = nc; }
+        if ((k & 1) == 0) c = 7 - c;
+        return r * 8 + c;
+    }
 };
 
 }  // namespace azg

@@ -1110,9 +1110,11 @@ __global__ __launch_bounds__(64) void k_emit_samples(View ev) {
         if (si >= ev.ex_cap) continue;
         typename G::S hs = G::load(&ev.hist_state[(size_t)slot * ev.max_hist + hI], lane);
         const float *hp = ev.hist_pi + ((size_t)slot * ev.max_hist + hI) * A;
-        typename G::S ss = G::symmetry(hs, kk);
+        // symmetricSamples off: the raw (state, pi) (SelfPlayAgent.pyx:187-190), the entry of symmetries() that is the identity
+        const int k = ev.symmetric ? kk : G::SYM_RAW;
+        typename G::S ss = G::symmetry(hs, k);
         G::template write_obs<float>(ss, ev.ex_obs + (size_t)si * G::OBS, lane);
-        for (int a = lane; a < A; a += 64) ev.ex_pi[(size_t)si * A + G::sym_action(a, kk)] = hp[a];
+        for (int a = lane; a < A; a += 64) ev.ex_pi[(size_t)si * A + G::sym_action(a, k)] = hp[a];
         if (lane < NV) ev.ex_z[(size_t)si * NV + lane] = (float)((ws >> lane) & 1);
     }
 }

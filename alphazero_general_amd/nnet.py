@@ -18,6 +18,8 @@ CONNECT4_NET_ARGS = dotdict(num_channels=128, depth=8, value_head_channels=32, p
                             value_dense_layers=[1024, 256], policy_dense_layers=[1024])           # envs/connect4/train.py:45-50
 BRANDUBH_NET_ARGS = dotdict(num_channels=64, depth=4, value_head_channels=16, policy_head_channels=16,
                             value_dense_layers=[1024, 128], policy_dense_layers=[1024])           # envs/hnefatafl/train_brandubh.py:50-55
+OTHELLO_NET_ARGS = dotdict(num_channels=64, depth=4, value_head_channels=16, policy_head_channels=16,
+                           value_dense_layers=[512, 256], policy_dense_layers=[512])             # envs/othello/train.py:25-30
 
 
 def _mlp(sizes):
@@ -404,9 +406,9 @@ class HipResNet:
     @property
     def can_search(self):
         """a persistent search launch exists for this network: connect4 x 128 channels with fused heads (azg_search_f16), or
-        factorised heads on brandubh x 64 / the 3-player env x 32 / connect4 x {32, 64} channels -- the reference's default net
-        (Coach.py:108-116) on connect4 is the 32-channel one -- (azg_search_wide_exact_f16 / azg_search_wide_f16)."""
-        return (self.fused_head and self.game == 0 and self.CH == 128) or (self.fact_head and (self.game, self.CH) in ((1, 64), (2, 32), (0, 32), (0, 64)))
+        factorised heads on brandubh x 64 / the 3-player env x 32 / connect4 x {32, 64} / othello x {32, 64} channels -- the reference's
+        default net (Coach.py:108-116) is the 32-channel one -- (azg_search_wide_exact_f16 / azg_search_wide_f16)."""
+        return (self.fused_head and self.game == 0 and self.CH == 128) or (self.fact_head and (self.game, self.CH) in ((1, 64), (2, 32), (0, 32), (0, 64), (3, 32), (3, 64)))
 
     def search(self, engine, sims, exact=False):
         """`sims` whole simulations (select -> this network -> backup) on every slot of `engine` in one persistent launch: the
@@ -634,7 +636,7 @@ class NNetWrapper:
         self._infer, self._graph, self._hip = net.eval(), None, None
         use_hip = self.backend == 'hip' or (self.backend == 'auto' and self.device.type == 'cuda'
                                             and (getattr(self.game_cls, 'AZG_GAME_ID', None), self.args.num_channels) in
-                                            ((0, 32), (0, 64), (0, 128), (1, 64), (1, 128), (2, 32)))
+                                            ((0, 32), (0, 64), (0, 128), (1, 64), (1, 128), (2, 32), (3, 32), (3, 64)))
         if use_hip:
             self._hip = HipResNet(FoldedResNet(self.nnet).to(self.device), self.game_cls.AZG_GAME_ID, self.device)
         return self

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define AZG_ABI_VERSION 6
+#define AZG_ABI_VERSION 7
 
 typedef enum azg_status {
     AZG_OK = 0,
@@ -46,11 +46,13 @@ typedef enum azg_status {
 typedef enum azg_game {
     AZG_GAME_CONNECT4 = 0,      /* alphazero/envs/connect4/connect4.pyx + Connect4Logic.pyx          */
     AZG_GAME_BRANDUBH = 1,      /* alphazero/envs/brandubh/fastafl.pyx + fastafl/cengine.pyx         */
-    AZG_GAME_TRIMOK = 2         /* build-defined 3-player env (N-player path, BASELINE config 5)     */
+    AZG_GAME_TRIMOK = 2,        /* build-defined 3-player env (N-player path, BASELINE config 5)     */
+    AZG_GAME_OTHELLO = 3        /* alphazero/envs/othello/othello.pyx + OthelloLogic.pyx (ABI v7)    */
 } azg_game;
 
 /* Game state as it crosses the ABI (all games): the reference's board array, row-major, one int8 per cell
- * (connect4: 1/-1/0 as Connect4Logic.pyx:34; brandubh: piece codes of fastafl/cengine.pyx:24-32),
+ * (connect4: 1/-1/0 as Connect4Logic.pyx:34; brandubh: piece codes of fastafl/cengine.pyx:24-32; othello: cells[8x + y] =
+ * pieces[x][y] of OthelloLogic.pyx:31-46, 1 = player 0's colour, -1 = player 1's, 0 = empty -- all 64 cells, action a plays cell a),
  * GameState._player / _turns (Game.py:10-11) and two game-specific words. */
 typedef struct azg_state {
     int8_t  cells[64];
