@@ -113,9 +113,9 @@ static void c4_symmetry(const azo_state *s, const float *pi, int k, azo_state *s
 /* ---- dispatch ---------------------------------------------------------------------------------- */
 int azo_game_info_get(int game, azo_game_info *o) {
     switch (game) {
-    case AZO_GAME_CONNECT4: *o = (azo_game_info){ 7, 4, 6, 7, 2, 1, 42, 2, 42 }; return 0;     /* connect4.pyx:11-17 */
-    case AZO_GAME_BRANDUBH: *o = (azo_game_info){ 588, 5, 7, 7, 2, 1, 100, 8, 49 }; return 0;  /* fastafl.pyx:34-41 + SURVEY Q19 */
-    case AZO_GAME_TRIMOK:   *o = (azo_game_info){ 25, 5, 5, 5, 3, 1, 25, 1, 25 }; return 0;    /* build-defined 3-player env */
+    case AZO_GAME_CONNECT4: *o = (azo_game_info){ 7, 4, 6, 7, 2, 1, 42, 2, 42, 0 }; return 0;     /* connect4.pyx:11-17, 96-99 */
+    case AZO_GAME_BRANDUBH: *o = (azo_game_info){ 588, 5, 7, 7, 2, 1, 100, 8, 49, 6 }; return 0;  /* fastafl.pyx:34-41 + SURVEY Q19; identity: rot90^4, no flip (:213-256) */
+    case AZO_GAME_TRIMOK:   *o = (azo_game_info){ 25, 5, 5, 5, 3, 1, 25, 1, 25, 0 }; return 0;    /* build-defined 3-player env */
     }
     return -1;
 }

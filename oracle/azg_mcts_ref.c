@@ -513,9 +513,10 @@ int azo_agent_play_moves(azo_agent *ag) {
                 if (!ag->args.is_arena) {                                             /* :184-196 */
                     for (int h = 0; h < ag->hist_len[i]; h++) {
                         int nsym = ag->args.symmetricSamples ? ag->gi.num_symmetries : 1;
-                        for (int k = 0; k < nsym; k++) {
+                        for (int k = 0; k < nsym; k++) {                      /* off: the raw (state, pi), :187-190 */
                             azo_state ss;
-                            azo_game_symmetry(ag->game, &ag->hist[i][h].st, ag->hist[i][h].pi, k, &ss, pis);
+                            azo_game_symmetry(ag->game, &ag->hist[i][h].st, ag->hist[i][h].pi,
+                                              ag->args.symmetricSamples ? k : ag->gi.raw_symmetry, &ss, pis);
                             azo_game_observation(ag->game, &ss, obs);
                             push_sample(ag, obs, pis, ws);
                         }

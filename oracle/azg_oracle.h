@@ -38,6 +38,7 @@ typedef struct azo_state {
 
 typedef struct azo_game_info {
     int32_t action_size, obs_c, obs_h, obs_w, num_players, has_draw, max_turns, num_symmetries, cells;
+    int32_t raw_symmetry;         /* the entry of symmetries() that is (state, pi) itself: the raw sample  */
 } azo_game_info;
 
 int  azo_game_info_get(int game, azo_game_info *out);
@@ -46,7 +47,8 @@ int  azo_game_play(int game, azo_state *s, int action);               /* 0 ok, <
 void azo_game_valid_moves(int game, const azo_state *s, uint8_t *valid /*[A]*/);
 void azo_game_win_state(int game, const azo_state *s, uint8_t *ws /*[P+1]*/);
 void azo_game_observation(int game, const azo_state *s, float *obs /*[C*H*W]*/);
-/* k-th symmetry of (state, pi): writes the transformed state and policy (k=0 is the identity).      */
+/* k-th entry of the game's symmetries(pi) list, in the reference's order: writes the transformed state and
+ * policy.  The identity is entry azo_game_info.raw_symmetry (brandubh: 6, fastafl.pyx:213-256), not always 0. */
 void azo_game_symmetry(int game, const azo_state *s, const float *pi, int k, azo_state *s_out, float *pi_out);
 
 /* ---- random tape (definition shared by oracle + product; see DESIGN.md "Random tape") -------- */

@@ -894,7 +894,8 @@ def main():
     if 'br_agent' in which:
         gen_agent(br_game_cls(), ol.GAME_BRANDUBH, 'br', seed=321,
                   configs=[('plain', 6, 12, 4, dict()), ('noisy', 4, 10, 3, dict(add_root_noise=True, add_root_temp=True)),
-                           ('wide', 16, 30, 10, dict())])
+                           ('wide', 16, 30, 10, dict()),
+                           ('raw', 6, 12, 4, dict(symmetricSamples=False, probFastSim=0.5, numFastSims=6))])   # raw samples: symmetries()[6] is the identity
 
 
 if __name__ == '__main__':

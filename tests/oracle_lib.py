@@ -30,7 +30,7 @@ class State(C.Structure):
 
 class GameInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('action_size', 'obs_c', 'obs_h', 'obs_w', 'num_players', 'has_draw',
-                                          'max_turns', 'num_symmetries', 'cells')]
+                                          'max_turns', 'num_symmetries', 'cells', 'raw_symmetry')]
 
 
 class MctsArgs(C.Structure):

@@ -709,14 +709,17 @@ def test_prior_spreads_from_denormal_to_one_vs_oracle(torch_mod, game, spread):
 
 
 @pytest.mark.parametrize('launch', LAUNCHES)
-@pytest.mark.parametrize('cname,kw', [('plain', dict()), ('noisy', dict(add_root_noise=True, add_root_temp=True)), ('wide', dict())])
+@pytest.mark.parametrize('cname,kw', [('plain', dict()), ('noisy', dict(add_root_noise=True, add_root_temp=True)), ('wide', dict()),
+                                      ('raw', dict(symmetric_samples=False))])           # raw: symmetries()[6] is the identity
 def test_br_agent_vs_reference_goldens(torch_mod, cname, kw, launch):
     torch = torch_mod
     d = dict(np.load(os.path.join(G, 'br_agent.npz')))              # (NpzFile decompresses an array on EVERY d[key])
     B, sims, games = int(d[cname + '_B']), int(d[cname + '_sims']), int(d[cname + '_games'])
     seed, slot_base = int(d[cname + '_seed']), int(d[cname + '_slot_base'])
     eng = engine(game=BR, B=B, seed=seed, slot_base=slot_base, games_per_iteration=games, example_capacity=20000, sims_hint=sims, **kw)
-    rec = run_engine_agent(torch, eng, seed, slot_base, sims, games, launch=launch)
+    rnd = dict(prob_fast=0.5, fast_sims=6) if cname == 'raw' else {}
+    rec = run_engine_agent(torch, eng, seed, slot_base, sims, games, launch=launch, **rnd)
+    assert (np.array(rec['sims']) == d[cname + '_round_sims']).all()
     assert (np.array(rec['counts']) == d[cname + '_counts']).all()
     assert (np.array(rec['actions']) == d[cname + '_actions']).all()
     assert (np.array(rec['games_played']) == d[cname + '_games_played']).all()

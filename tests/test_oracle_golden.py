@@ -523,7 +523,8 @@ def test_br_tree_vs_reference(cname):
         assert ol.lib().azo_mcts_tape_ctr(m.h) == d[cname + '_ctr'][r]
 
 
-@pytest.mark.parametrize('cname,kw', [('plain', dict()), ('noisy', dict(add_root_noise=True, add_root_temp=True)), ('wide', dict())])
+@pytest.mark.parametrize('cname,kw', [('plain', dict()), ('noisy', dict(add_root_noise=True, add_root_temp=True)), ('wide', dict()),
+                                     ('raw', dict(symmetric=False, prob_fast=0.5, fast_sims=6))])   # raw: symmetries()[6] is the identity
 def test_br_agent_vs_reference(cname, kw):
     d = dict(np.load(os.path.join(G, 'br_agent.npz')))              # (NpzFile decompresses an array on EVERY d[key])
     ag, rec = run_oracle_agent(BR, d, cname, kw)
