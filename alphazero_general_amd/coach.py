@@ -8,8 +8,10 @@
 `native_coach` returns a subclass that overrides EXACTLY the five methods learn() calls for self-play -- generateSelfPlayAgents,
 processSelfPlayBatches, saveIterationSamples, processGameResults, killSelfPlayAgents (Coach.py:291,326,364,389,401) -- and rebinds the
 name `Arena` in the Coach's module to `native_arena(Arena)`, whose play_games takes the batched branch (Arena.pyx:223-328) to the
-device when every player is a model player of a game with device rules.  Everything else -- train(), gating, checkpoints, the
-TensorBoard writer, compareToBaseline against non-model players -- runs the reference's code.  No agent processes, no shared
+device when every player is a model player or the reference's RawMCTSPlayer (compareToBaseline's default baselineTester, Coach.py:70,
+575-584: a raw seat, evaluated on the device with RawMCTSPlayer.process's constants) of a game with device rules.  Everything else --
+train(), gating, checkpoints, the TensorBoard writer, compareToBaseline against other non-model players (RandomPlayer, unbatched
+arenas) -- runs the reference's code; native_coach(..., raw_seats=False) sends RawMCTSPlayer arenas there too.  No agent processes, no shared
 tensors, no queues: the games live on the GPU(s) (iteration.run_iteration / run_arena), the live net's weights are adopted in
 memory (NNetWrapper.adopt), and the three sample files the unchanged Coach.train loads (:442-456) are written by rank 0.
 
@@ -51,7 +53,7 @@ class _NetCache:
         return w.adopt(ref_net)
 
 
-def native_coach(Coach, *, device=None, install_arena=True):
+def native_coach(Coach, *, device=None, install_arena=True, raw_seats=True):
     """class factory: the reference's Coach with its self-play phase on the device engine (see the module docstring)"""
     cmod = sys.modules[Coach.__module__]
     TrainState = getattr(cmod, 'TrainState', None)
@@ -120,26 +122,38 @@ def native_coach(Coach, *, device=None, install_arena=True):
 
     NativeCoach.__name__ = NativeCoach.__qualname__ = 'Native' + Coach.__name__
     if install_arena and hasattr(cmod, 'Arena'):
-        cmod.Arena = native_arena(cmod.Arena, device=device)
+        cmod.Arena = native_arena(cmod.Arena, device=device, raw_seats=raw_seats)
     return NativeCoach
 
 
-def native_arena(Arena, *, device=None):
-    """class factory: the reference's Arena whose batched play_games runs on the device when it can (all players carry a model `.nn`,
-    Arena was built with use_batched_mcts, the game has device rules); anything else falls through to the reference's own code."""
+def is_raw_player(p):
+    """the reference's RawMCTSPlayer itself (recognised by module and class name, like the env classes; a subclass or an instance with
+    its own `process` is not): its batched evaluation is constant (GenericPlayers.py:198-200), so the engine plays it as a raw seat"""
+    t = type(p)
+    return t.__name__ == 'RawMCTSPlayer' and t.__module__.rsplit('.', 1)[-1] == 'GenericPlayers' and 'process' not in vars(p)
+
+
+def native_arena(Arena, *, device=None, raw_seats=True):
+    """class factory: the reference's Arena whose batched play_games runs on the device when it can (every player carries a model `.nn`
+    or is a RawMCTSPlayer -- a raw seat; raw_seats=False: such arenas fall through --, Arena was built with use_batched_mcts, the game has
+    device rules); anything else falls through to the reference's own code."""
     if getattr(Arena, '_azg_native', False):
-        return Arena
+        if Arena._azg_raw_seats == raw_seats:
+            return Arena
+        Arena = Arena._azg_base                                      # (the other raw-seat choice: wrap the reference's class afresh)
 
     class NativeArena(Arena):
         _azg_native = True
+        _azg_raw_seats, _azg_base = raw_seats, Arena
 
         def play_games(self, num, verbose=False, shuffle_players=True):          # Arena.pyx:188-376
             g = _ours(self.game_cls)
             nets = [getattr(p, 'nn', None) for p in self.players]
-            if not self.use_batched_mcts or g is None or any(n is None for n in nets):
+            raw = [n is None and raw_seats and is_raw_player(p) for p, n in zip(self.players, nets)]
+            if not self.use_batched_mcts or g is None or all(raw) or any(n is None and not r for n, r in zip(nets, raw)):
                 return Arena.play_games(self, num, verbose, shuffle_players)
             cache = _NetCache(g, device)
-            ours = [cache.get(n) for n in nets]                      # (one wrapper per distinct reference net: [new] + [past] * (P - 1))
+            ours = [None if r else cache.get(n) for n, r in zip(nets, raw)]     # (None: a raw seat)                      # (one wrapper per distinct reference net: [new] + [past] * (P - 1))
             self.total_games = num
             r = it_mod.lead('arena', g, ours, self.args, num_games=num, details=True,
                             seats='slot' if shuffle_players else 'agent', stop=self.stop_event.is_set)

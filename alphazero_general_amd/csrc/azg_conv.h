@@ -449,6 +449,18 @@ template <class G> struct SearchArena { View ev; int sims; SeatMap seat; const u
 template <class G, int MINB = 1, bool EXACT_ = false> struct SearchWide {
     View ev; int sims; HeadRows hd; HeadsFull hf;
     using Game = G; static constexpr bool WIDE = true; static constexpr int MIN_BLOCKS = MINB; static constexpr bool EXACT = EXACT_;
+    static constexpr bool ARENA = false;
+};
+// The batched Arena on the wide search mode (exact heads, the one-game tile of each (game, width)): wave 0 walks the MOVER's tree
+// (slot * T + mover, as tree_of_slot), the workgroup evaluates with the mover's model -- seat.v[mover] or seat_of_slot, as SearchArena --
+// whose parameters, tower AND heads, come from m[model].  A model whose pointers are all null is a RAW seat (RawMCTSPlayer.process,
+// GenericPlayers.py:198-200): policy float32(1 / A) for every action, value zeros; its workgroup runs no tower and no heads, and its tree
+// phase masks and renormalises the constant row like azg_backup (MCTS.pyx:239-245).  Mover, tree and model are fixed for the launch.
+struct WideModel { const void *w; const float *bias, *pre_scale, *pre_shift; const void *head1_w; const float *head1_b; HeadsFull hf; };
+struct WideArenaArgs { View ev; int sims; HeadRows hd; HeadsFull hf; SeatMap seat; const uint32_t *seat_of_slot; int nmodels; WideModel m[4]; };
+template <class G, int MINB> struct SearchWideArena : WideArenaArgs {
+    using Game = G; static constexpr bool WIDE = true; static constexpr int MIN_BLOCKS = MINB; static constexpr bool EXACT = true;
+    static constexpr bool ARENA = true;
 };
 
 // OVERLAPPED one-game tile (exact heads, four wavefronts, a wide policy head: brandubh up to 512 games per GPU).  The heads phase is a
@@ -674,6 +686,8 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
     static_assert(!IS_SEARCH || IS_WIDE || (PSPLIT == 1 && C == 128 && BOARDS <= C / 32), "search mode: one wave per game, fused heads");
     constexpr bool IS_ARENA = []() { if constexpr (IS_SEARCH) { if constexpr (!SEARCH::WIDE) return SEARCH::ARENA; } return false; }();
     static_assert(!IS_ARENA || BOARDS == 1, "arena search: one game (one mover, one model) per workgroup");
+    constexpr bool IS_WARENA = []() { if constexpr (IS_SEARCH) { if constexpr (SEARCH::WIDE) return SEARCH::ARENA; } return false; }();
+    static_assert(!IS_WARENA || BOARDS == 1, "wide arena search: one game (one mover, one model) per workgroup");
     static_assert(!IS_WIDE || (C / 32) * PSPLIT * KSPLIT >= BOARDS, "wide search mode: at least one wavefront per game");
     constexpr bool SOLO = IS_WIDE && wide_solo<C, PSPLIT, KSPLIT, BOARDS>();
     constexpr bool EXACT = []() { if constexpr (IS_WIDE) return SEARCH::EXACT; else return false; }();
@@ -791,6 +805,23 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
                 P.w = Pin.w; P.bias = Pin.bias; P.pre_scale = Pin.pre_scale; P.pre_shift = Pin.pre_shift; P.head_w = Pin.head_w; P.head_b = Pin.head_b;
             }
         }
+        // (wide search: the heads' parameters of this launch; the wide arena replaces them, and the tower's, by the mover's model)
+        // (wide arena: mover | raw << 4 also goes to LDS beside the error word -- read back where it is used, so that it takes no register
+        //  across the simulation loop: the kernel is at its register budget)
+        [[maybe_unused]] HeadsFull hfs{};
+        [[maybe_unused]] bool raw = false;                       // (wide arena: the mover's seat has no network)
+        if constexpr (IS_WIDE) hfs = sa.hf;
+        if constexpr (IS_WARENA) {
+            const int sl = min(gtile, sa.ev.B - 1);
+            const int wmover = __builtin_amdgcn_readfirstlane((int)sa.ev.states[sl].player);
+            int m = __builtin_amdgcn_readfirstlane(sa.seat_of_slot ? (int)((sa.seat_of_slot[sl] >> (4 * wmover)) & 15u) : sa.seat.v[wmover & 7]);
+            if (m < 0 || m >= sa.nmodels) m = 0;
+            const WideModel &M = sa.m[m];
+            P.w = M.w; P.bias = M.bias; P.pre_scale = M.pre_scale; P.pre_shift = M.pre_shift; P.head1_w = M.head1_w; P.head1_b = M.head1_b;
+            hfs = M.hf;
+            raw = M.w == nullptr;
+            if (tid == 0) reinterpret_cast<int *>(smem + TILE + WideLds<typename SEARCH::Game, GEO::HW, BOARDS, SOLO>::ERR)[1] = wmover | (raw ? 16 : 0);
+        }
         const half8 *wl = reinterpret_cast<const half8 *>(P.w) + (size_t)(2 * cg) * 64 + lane;
         const half8 *wm0 = wl + (size_t)(STEM_KSTEPS + (KSPLIT == 2 ? kg : 0)) * GEO::WSTEP;      // the wave's main stream (see stream_frag)
         const int row0 = tile * ROWS;
@@ -799,7 +830,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
         if constexpr (IS_SEARCH) nsims = sa.sims + (IS_WIDE ? 1 : 0);  // (wide: the last iteration is the last backup, no tower)
         [[maybe_unused]] const int sc_off = PARAM_OFF + (2 * P.nblocks + 1) * C * 4, sh_off = sc_off + P.nblocks * C * 2;
         [[maybe_unused]] const int h1_off = PARAM_OFF + tower_layer_param_bytes<C, BOARDS>(P.nblocks);
-        if constexpr (PLDS) {                                    // this tile's model: biases and affines -> LDS (read after the barrier that precedes the layers)
+        if (PLDS && !raw) {                                      // this tile's model: biases and affines -> LDS (read after the barrier that precedes the layers)
             float *pb_ = reinterpret_cast<float *>(smem + PARAM_OFF);
             _Float16 *psc_ = reinterpret_cast<_Float16 *>(smem + sc_off), *psh_ = reinterpret_cast<_Float16 *>(smem + sh_off);
             for (int c = tid; c < (2 * P.nblocks + 1) * C; c += NT) pb_[c] = P.bias[c];
@@ -849,13 +880,20 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
             int slot = tile * BOARDS + bd;
             asm volatile("" : "+v"(slot));                       // (opaque: nothing of the trees is hoisted out of the simulation loop)
             slot = __builtin_amdgcn_readfirstlane(slot);
+            int wsel = 0;                                        // (wide arena: mover | raw << 4, written before the barrier of simulation 0)
+            if constexpr (IS_WARENA) {
+                wsel = reinterpret_cast<const int *>(errw)[1];
+                asm volatile("" : "+v"(wsel));
+                wsel = __builtin_amdgcn_readfirstlane(wsel);
+            }
+            const bool raw = (wsel >> 4) != 0;
             // (k-split workgroups have wavefronts to spare in the tree phase: the third one takes the shuffle masks off the helper)
             constexpr bool MASK_WAVE = NT / 64 >= 3 * BOARDS;
             // (and the fourth one runs the game rules one level behind the walk: WalkMail, azg_kernels.h)
             constexpr bool RULES_WAVE = NT / 64 >= 4 * BOARDS;
             const bool livegame = slot < sa.ev.B && role < (SOLO ? 1 : RULES_WAVE ? 4 : MASK_WAVE ? 3 : 2);
             [[maybe_unused]] WalkMail *mail = reinterpret_cast<WalkMail *>(ws + WS::MAIL);
-            const int tree = slot;                               // (self-play engines only: one tree per slot)
+            const int tree = IS_WARENA ? slot * sa.ev.T + (wsel & 15) : slot;   // (self-play: one tree per slot; arena: the mover's, tree_of_slot)
             // The tree functions reach the header, the path, the tape counter, the tallies and the root state through the View's
             // pointers: here those point into the game's LDS scratch (offset so that [tree] / [slot] lands on it), so that every
             // simulation's header / path / counter reads are LDS reads instead of a chain of three or four L2 round trips (4 k
@@ -921,6 +959,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
                                 leaf_policy_logits<G, false>(sa.hd, nodes, hr.leaf_fc, hr.leaf_k, reinterpret_cast<const _Float16 *>(ws + WS::FEAT), lg, lane);
                                 wave_sync();
                             }
+                            if (raw) raw_policy_row<A>(lane, pi); else
                             policy_softmax_row<A>(lg, lane, A, pi);
                             wave_sync();
                             backup_policy<G>(evl, slot, hr, nodes, pi, reinterpret_cast<float *>(ws + WS::M), reinterpret_cast<float *>(ws + WS::SCR), lane);
@@ -941,7 +980,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
                             wave_sync();
                         }
                         if constexpr (OVL) flag_wait_gen(sa.ev, &flags[3], sim);     // (the streaming wavefront's first subtile)
-                        pv = value_softmax(lg + A, lane, NV);
+                        if (!raw) pv = value_softmax(lg + A, lane, NV);          // (a raw seat's value row is zeros)
                     }
 #pragma unroll
                     for (int j = 0; j < NV; j++) val[j] = rl(pv, j);
@@ -1013,6 +1052,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
                     }
                     if constexpr (OVL) flag_wait_gen(sa.ev, &flags[2], sim);         // (the other streaming wavefront's policy subtiles)
                     AZG_HSTAMP(3);
+                    if (raw) raw_policy_row<A>(lane, pi); else
                     policy_softmax_row<A>(lg, lane, A, pi);
                     wave_sync();
                     AZG_HSTAMP(4);
@@ -1033,6 +1073,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
             }
             if (sim == sa.sims) break;                           // the last backup is done: no evaluation follows
             AZG_WPHASE(1);
+            if (raw) { __syncthreads(); continue; }              // (wide arena, raw seat: nothing to evaluate; the barrier stands for the tower's)
         } else if constexpr (IS_SEARCH) {
             using G = typename SEARCH::Game;
             static_assert(G::CELLS == HW && G::A < 8, "search mode needs a game whose tree functions use no LDS scratch");
@@ -1256,13 +1297,13 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
             //  brandubh 512 games 7.24 -> 7.03 ms per move, 2048 games 15.19 -> 15.61 with it, same box)
             constexpr bool HEADS_EARLY = EXACT && BOARDS == 1;
             if constexpr (OVL) {                                 // (the streaming wavefronts; items instead of subtiles: value first)
-                if (wave >= 1 && wave <= OVL_NW) heads_full_prefetch<typename SEARCH::Game, HW, OVL_NW, true>(sa.hf, wave - 1, lane, hfirst);
+                if (wave >= 1 && wave <= OVL_NW) heads_full_prefetch<typename SEARCH::Game, HW, OVL_NW, true>(hfs, wave - 1, lane, hfirst);
                 if (IS_WIDE && tid == 0 && (sim & 15) == 15) {   // (the sticky-error look, every 16th simulation: read behind the barrier below)
                     using WLE = WideLds<typename WideGameOf<SEARCH>::type, HW, BOARDS, SOLO>;
                     *reinterpret_cast<int *>(smem + TILE + WLE::ERR) = sa_error_word(sa);
                 }
             } else
-            if constexpr (HEADS_EARLY) heads_full_prefetch<typename SEARCH::Game, HW, NT / 64>(sa.hf, wave, lane, hfirst);
+            if constexpr (HEADS_EARLY) heads_full_prefetch<typename SEARCH::Game, HW, NT / 64>(hfs, wave, lane, hfirst);
             if (cg == 0) {
                 int opaque = 0;
                 asm volatile("" : "+s"(opaque));                 // (keeps these loop invariants from being hoisted across the layers)
@@ -1321,15 +1362,15 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
                     if ((sim & 15) == 15 && *reinterpret_cast<const int *>(smem + TILE + WLO::ERR)) break;   // (uniform: every wavefront reads the word behind the barrier)
                     int *flags_ = reinterpret_cast<int *>(smem + TILE + WSO::FLAGS);
                     if (wave >= 1 && wave <= OVL_NW) {
-                        heads_full_lds<typename SEARCH::Game, HW, BOARDS, OVL_NW, SOLO, true>(smem + TILE, smem + TILE + WLO::ZERO, sa.hf, wave - 1, lane, hfirst, &flags_[3], sim + 1);
+                        heads_full_lds<typename SEARCH::Game, HW, BOARDS, OVL_NW, SOLO, true>(smem + TILE, smem + TILE + WLO::ZERO, hfs, wave - 1, lane, hfirst, &flags_[3], sim + 1);
                         if (wave == 2) flag_set_gen(&flags_[2], sim + 1, lane);
                     }
                 } else if constexpr (HEADS_EARLY) {
-                    heads_full_lds<typename SEARCH::Game, HW, BOARDS, NT / 64, SOLO>(smem + TILE, smem + TILE + WideLds<typename SEARCH::Game, HW, BOARDS, SOLO>::ZERO, sa.hf, wave, lane, hfirst);
+                    heads_full_lds<typename SEARCH::Game, HW, BOARDS, NT / 64, SOLO>(smem + TILE, smem + TILE + WideLds<typename SEARCH::Game, HW, BOARDS, SOLO>::ZERO, hfs, wave, lane, hfirst);
                 } else if constexpr (EXACT) {
                     HeadsFirst<typename SEARCH::Game, HW> hl;
-                    heads_full_prefetch<typename SEARCH::Game, HW, NT / 64>(sa.hf, wave, lane, hl);
-                    heads_full_lds<typename SEARCH::Game, HW, BOARDS, NT / 64, SOLO>(smem + TILE, smem + TILE + WideLds<typename SEARCH::Game, HW, BOARDS, SOLO>::ZERO, sa.hf, wave, lane, hl);
+                    heads_full_prefetch<typename SEARCH::Game, HW, NT / 64>(hfs, wave, lane, hl);
+                    heads_full_lds<typename SEARCH::Game, HW, BOARDS, NT / 64, SOLO>(smem + TILE, smem + TILE + WideLds<typename SEARCH::Game, HW, BOARDS, SOLO>::ZERO, hfs, wave, lane, hl);
                 }
                 AZG_WPHASE(4);
 #ifdef AZG_TOWER_TIMING
@@ -1446,15 +1487,16 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
             using WS = WideScratch<G, HW, SOLO>;
             __syncthreads();
             const int bd = wave % BOARDS, role = wave / BOARDS, slot = tile * BOARDS + bd;
+            const int tree = IS_WARENA ? slot * sa.ev.T + (reinterpret_cast<const int *>(smem + TILE + WideLds<G, HW, BOARDS, SOLO>::ERR)[1] & 15) : slot;
             if (lds_live && role == 0 && slot < sa.ev.B) {
                 const char *ws = smem + TILE + bd * WS::BYTES;
-                if (lane < 4) reinterpret_cast<uint4 *>(sa.ev.hdr + slot)[lane] = reinterpret_cast<const uint4 *>(ws + WS::HDR)[lane];
+                if (lane < 4) reinterpret_cast<uint4 *>(sa.ev.hdr + tree)[lane] = reinterpret_cast<const uint4 *>(ws + WS::HDR)[lane];
                 static_assert(sizeof(TreeHdr) == 4 * sizeof(uint4) && sizeof(azg_state) % 16 == 0 && sizeof(PathEnt) == sizeof(uint4),
                               "the LDS mirror moves the header, the root state and the path as whole 16-byte chunks");
                 if constexpr (!SOLO) {
                     const int depth = *reinterpret_cast<const int *>(ws + WS::HDR + offsetof(TreeHdr, depth));
                     for (int j = lane; j < depth && j < sa.ev.maxd; j += 64)
-                        reinterpret_cast<uint4 *>(sa.ev.path + (size_t)slot * sa.ev.maxd)[j] = reinterpret_cast<const uint4 *>(ws + WS::PATH)[j];
+                        reinterpret_cast<uint4 *>(sa.ev.path + (size_t)tree * sa.ev.maxd)[j] = reinterpret_cast<const uint4 *>(ws + WS::PATH)[j];
                 }
                 if (lane == 0) {
                     sa.ev.tape_ctr[slot] = *reinterpret_cast<const uint64_t *>(ws + WS::CTR);

@@ -341,6 +341,12 @@ AZG_DEV void policy_softmax_row(const float *lg, int lane, int A, float *pol) {
 #pragma unroll
     for (int j = 0; j < NJ; j++) { const int o = lane + 64 * j; if (o < A) pol[o] = x[j] * inv; }
 }
+// a raw seat's policy row (RawMCTSPlayer.process, GenericPlayers.py:198-200: torch.full(1 / A), float32) -- NOT the warm-up constants
+template <int A>
+AZG_DEV void raw_policy_row(int lane, float *pol) {
+    constexpr float p = (float)(1.0 / A);                      // (the double 1 / A rounded once to float32, as torch.full does)
+    for (int o = lane; o < A; o += 64) pol[o] = p;
+}
 // the same for the NV <= 64 value logits lg[0 .. NV): lane j < NV returns probability j (other lanes 0)
 AZG_DEV float value_softmax(const float *lg, int lane, int NV) {
     const float v = lg[min(lane, NV - 1)];

@@ -1404,6 +1404,66 @@ extern "C" int azg_search_wide_exact_f16(azg_engine *e, void *stream, const void
                              HeadsFull{(const half8 *)wps_packed, (const half8 *)wv_packed, head_b}, feat_k, sims);
 }
 
+// the wide arena launch: the one-game tile of each (game, width) -- the self-play launch's bt == 1 shape (arena shards are small: the
+// default arenaCompare of 128 games is below the CU count), no tile autotune
+template <class G, int C, int PSPLIT, int MINB, int KSPLIT>
+static int wide_arena_tile(hipStream_t s, const TowerParams &P, const WideArenaArgs &a, bool init) {
+    SearchWideArena<G, MINB> sa;
+    static_cast<WideArenaArgs &>(sa) = a;
+    return launch_tower<G::H, G::W, 1, C, PSPLIT, SearchWideArena<G, MINB>, KSPLIT>(s, P, sa, init);
+}
+
+extern "C" int azg_search_arena_wide_exact_f16(azg_engine *e, void *stream, int nmodels, const void *const *w, const float *const *bias,
+                                               const float *const *pre_scale, const float *const *pre_shift, int nblocks, int channels,
+                                               const void *const *head1_w, const float *const *head1_b, const void *const *wps,
+                                               const void *const *wv, const float *const *head_b, int feat_k, const int32_t *p2i_host,
+                                               const uint32_t *seat_of_slot, int sims) {
+    if (!e || !w || !bias || !pre_scale || !pre_shift || !head1_w || !head1_b || !wps || !wv || !head_b || nblocks < 0 || sims < 0 || (!p2i_host && !seat_of_slot))
+        return fail(AZG_E_INVALID_ARG, "null or out-of-range argument");
+    const int game = e->cfg.game;
+    if (!e->v.arena || wide_max_tile(game, channels) == 0)
+        return fail(AZG_E_UNSUPPORTED, "the persistent wide arena launch is built for arena engines on brandubh x 64, the 3-player env x 32, connect4 x {32, 64} "
+                                       "and othello x {32, 64} channels (use azg_select / network / azg_backup)");
+    if (nmodels < e->gi.num_players || nmodels > 4) return fail(AZG_E_INVALID_ARG, "one model per player, at most 4");
+    const int A = e->gi.action_size, NV = e->gi.num_players + 1, hw = e->gi.obs_h * e->gi.obs_w;
+    if (feat_k != (hw * 16 + 31) / 32 * 32) return fail(AZG_E_INVALID_ARG, "feat_k must be H*W*16 rounded up to 32");
+    WideArenaArgs sa0{};
+    sa0.ev = e->v; sa0.sims = sims; sa0.hd = HeadRows{nullptr, nullptr, feat_k}; sa0.seat_of_slot = seat_of_slot; sa0.nmodels = nmodels;
+    int real = -1;
+    for (int m = 0; m < nmodels; m++) {
+        const bool ps = nblocks == 0 || (pre_scale[m] && pre_shift[m]), ps_null = nblocks == 0 || (!pre_scale[m] && !pre_shift[m]);
+        const bool all = w[m] && bias[m] && ps && head1_w[m] && head1_b[m] && wps[m] && wv[m] && head_b[m];
+        const bool none = !w[m] && !bias[m] && ps_null && !head1_w[m] && !head1_b[m] && !wps[m] && !wv[m] && !head_b[m];
+        if (!all && !none) return fail(AZG_E_INVALID_ARG, "a model's parameters must be all set (a network) or all null (a raw seat)");
+        if (all) {
+            sa0.m[m] = WideModel{w[m], bias[m], nblocks ? pre_scale[m] : nullptr, nblocks ? pre_shift[m] : nullptr, head1_w[m], head1_b[m],
+                                 HeadsFull{(const half8 *)wps[m], (const half8 *)wv[m], head_b[m]}};
+            if (real < 0) real = m;
+        }
+    }
+    if (p2i_host) for (int i = 0; i < e->gi.num_players && i < 8; i++) {
+        if (p2i_host[i] < 0 || p2i_host[i] >= nmodels) return fail(AZG_E_INVALID_ARG, "player_to_index entry out of range");
+        sa0.seat.v[i] = p2i_host[i];
+    }
+    // (P: the shape of the launch -- boards, depth, heads form; the parameters every workgroup reads are its model's, sa.m)
+    const WideModel &M0 = sa0.m[real < 0 ? 0 : real];
+    TowerParams P{nullptr, M0.w, M0.bias, M0.pre_scale, M0.pre_shift, nullptr, e->v.B, nblocks, nullptr, nullptr, nullptr, nullptr, A, NV, nullptr,
+                  M0.head1_w, M0.head1_b, nullptr, feat_k, nullptr, 0, {}};
+    hipStream_t s = (hipStream_t)stream;
+    const bool init = sims == 0;                                  // sims == 0: set up only
+    EvPair ep; const bool prof = !init && netprof_begin(s, ep);
+    int r = AZG_E_UNSUPPORTED;
+    if (game == AZG_GAME_BRANDUBH && channels == 64) r = wide_arena_tile<BR, 64, 1, 2, 2>(s, P, sa0, init);
+    else if (game == AZG_GAME_TRIMOK && channels == 32) r = wide_arena_tile<TM, 32, 2, 1, 1>(s, P, sa0, init);
+    else if (game == AZG_GAME_CONNECT4 && channels == 32) r = wide_arena_tile<C4, 32, 2, 1, 1>(s, P, sa0, init);
+    else if (game == AZG_GAME_CONNECT4 && channels == 64) r = wide_arena_tile<C4, 64, 2, 2, 1>(s, P, sa0, init);
+    else if (game == AZG_GAME_OTHELLO && channels == 32) r = wide_arena_tile<OT, 32, 2, 1, 1>(s, P, sa0, init);
+    else if (game == AZG_GAME_OTHELLO && channels == 64) r = wide_arena_tile<OT, 64, 1, 2, 2>(s, P, sa0, init);
+    if (r == AZG_E_UNSUPPORTED) { g_kev = nullptr; return fail(r, "persistent wide arena launch: no tile for this game / width"); }
+    if (!init) netprof_end(s, 2, prof, ep);
+    return r;
+}
+
 extern "C" int azg_policy_value_heads_f16(void *stream, const void *y, const void *head_w_packed, const float *head_b, int boards, int k,
                                           int A, int NV, float *logits_ws, float *policy, float *value) {
     if (!y || !head_w_packed || !head_b || !logits_ws || (!policy != !value)) return fail(AZG_E_INVALID_ARG, "null argument");

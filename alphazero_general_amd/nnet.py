@@ -501,6 +501,29 @@ class HipResNet:
                                             arr([n.tower_ps for n in nets]), arr([n.tower_pt for n in nets]), len(n0.blocks),
                                             arr([n.head_w_packed for n in nets]), arr([n.head_b16 for n in nets]), p2i, seats, int(sims)))
 
+    @staticmethod
+    def search_arena_wide(nets, engine, sims, player_to_index=None, slot_seats=None):
+        """search_arena for factorised-head networks (azg_search_arena_wide_exact_f16: the pairs `can_search` lists, exact heads -- the
+        bits NNetWrapper.process returns).  A None entry of `nets` is a raw seat: RawMCTSPlayer.process's constants (policy float32(1 / A),
+        value zeros), no network runs for its games.  The real models must share (game, tower width, depth, feat_k)."""
+        import ctypes as C
+        real = [n for n in nets if n is not None]
+        if not real:
+            raise ValueError('the wide arena launch needs at least one network')
+        n0 = real[0]
+        for n in real:
+            if not (n.fact_head and n.can_search):
+                raise NotImplementedError('the persistent wide arena launch needs factorised-head networks the persistent search supports')
+            assert (n.game, n.CH, len(n.blocks), n.feat_k, n.A, n.NV) == (n0.game, n0.CH, len(n0.blocks), n0.feat_k, n0.A, n0.NV)
+        arr = lambda f: (C.c_void_p * len(nets))(*[0 if n is None else f(n).data_ptr() for n in nets])
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        p2i = None if player_to_index is None else (C.c_int32 * len(player_to_index))(*[int(x) for x in player_to_index])
+        seats = None if slot_seats is None else C.c_void_p(slot_seats.data_ptr())
+        n0._check(n0.L.azg_search_arena_wide_exact_f16(
+            engine.h, st, len(nets), arr(lambda n: n.tower_w), arr(lambda n: n.tower_b), arr(lambda n: n.tower_ps), arr(lambda n: n.tower_pt),
+            len(n0.blocks), int(n0.CH), arr(lambda n: n.head1_w), arr(lambda n: n.head1_b), arr(lambda n: n.head2_wps),
+            arr(lambda n: n.head2_wv), arr(lambda n: n.head2_b), int(n0.feat_k), p2i, seats, int(sims)))
+
     def to_nhwc8(self, batch):
         """[B, C, H, W] (any float dtype) -> [B, H*W, 8] fp16."""
         B, C = batch.shape[0], batch.shape[1]

@@ -312,7 +312,13 @@ class ArenaRunner:
     167-168).  One engine with one tree per player per game; every simulation the leaf rows are grouped by model
     (player_to_index[mover]), each model evaluates its own contiguous slice, and the results are routed back with the
     correct row <-> game map (the reference's mis-routing, SURVEY.md Q15, is not reproduced).  Returns the
-    (wins, draws, winrates) contract of Arena.play_games (:376) via get_game_results semantics (utils.py:34-54)."""
+    (wins, draws, winrates) contract of Arena.play_games (:376) via get_game_results semantics (utils.py:34-54).
+    A None entry of `nnets` is a raw seat: the batched evaluation of the reference's RawMCTSPlayer.process (GenericPlayers.py:198-200),
+    policy float32(1 / A) for every action and value zeros.
+
+    A move runs as ONE persistent launch where one exists (fused_search=None picks it, True insists on it): azg_search_arena_wide_exact_f16
+    when every network has factorised heads the persistent search supports (raw seats included), azg_search_arena_f16 for connect4 x 128
+    fused-head networks without raw seats; otherwise per simulation (select / the models / backup)."""
 
     def __init__(self, game_cls, nnets, args, *, num_slots, seed=0, slot_base=0, device=None, use_graph=True, result_capacity=None,
                  seats='agent', nodes_per_tree=0, fused_search=None):
@@ -321,6 +327,9 @@ class ArenaRunner:
         self.B = int(num_slots)
         P = game_cls.num_players()
         assert len(self.nnets) == P
+        self.real = [n for n in self.nnets if n is not None]
+        assert self.real, 'an arena needs at least one network'
+        self.raw_seats = len(self.real) < P
         self.seed, self.slot_base = int(seed), int(slot_base)
         # seat permutation, one per agent, drawn from the agent-level tape stream (SelfPlayAgent.pyx:44-47)
         import ctypes as C
@@ -353,22 +362,28 @@ class ArenaRunner:
             self.slot_player_to_index = perm                        # [slot][player] -> model
             packed = [sum(m[p] << (4 * p) for p in range(P)) for m in perm]
             self.slot_seats = torch.tensor(packed, dtype=torch.int32, device=e.device)
-        hip = all(getattr(n, '_hip', None) is not None or (n.refresh() and n._hip is not None) for n in self.nnets)
+        hip = all(getattr(n, '_hip', None) is not None or (n.refresh() and n._hip is not None) for n in self.real)
         self.nhwc8 = bool(hip)
         self.obs = (torch.zeros((self.B, e.gi.obs_h * e.gi.obs_w, 8), dtype=torch.float16, device=e.device) if self.nhwc8
                     else e.new_obs(torch.float16))
         self.policy = torch.zeros((self.B, e.A), dtype=torch.float32, device=e.device)
         self.value = torch.zeros((self.B, e.NV), dtype=torch.float32, device=e.device)
-        # fused tower + heads on every model: the per-model batch split never leaves the device
-        self.device_split = bool(hip) and all(n._hip.fused_head for n in self.nnets)
+        # factorised heads the persistent search supports, on every network: a whole move as ONE persistent launch
+        # (azg_search_arena_wide_exact_f16: one game per workgroup, the mover's tree, the mover's model or a raw seat's constants)
+        h0 = self.real[0]._hip if hip else None
+        can_wide = bool(hip) and all(n._hip.fact_head and n._hip.can_search and (n._hip.game, n._hip.CH, len(n._hip.blocks), n._hip.feat_k)
+                                     == (h0.game, h0.CH, len(h0.blocks), h0.feat_k) for n in self.real)
+        # fused tower + heads on every model (no raw seat): the per-model batch split never leaves the device
+        self.device_split = bool(hip) and not self.raw_seats and all(n._hip.fused_head for n in self.nnets)
         # a whole move as ONE persistent launch (azg_search_arena_f16: one game per workgroup, the mover's tree, the mover's model) where the
         # models have it -- connect4 x 128 channels --, else one multi-model tower launch + one tree launch per simulation
         can = self.device_split and self.game == 0 and all(n._hip.CH == 128 for n in self.nnets)
-        if fused_search and not can:
+        if fused_search and not (can or can_wide):
             raise NotImplementedError('no persistent arena launch for these models / this game')
-        self.fused_search = can if fused_search is None else bool(fused_search)
+        self.wide_search = can_wide and fused_search is not False
+        self.fused_search = can if fused_search is None else bool(fused_search) and can
         self._graph = None
-        if self.device_split and use_graph:
+        if (self.device_split or self.wide_search) and use_graph:
             self.capture()
 
     def _rows(self):
@@ -385,7 +400,9 @@ class ArenaRunner:
         counts = rpm.cpu().tolist()                                  # host read of the batch split, once per simulation
         off = 0
         for mi, n in enumerate(counts):
-            if n:
+            if n and self.nnets[mi] is None:                         # raw seat: RawMCTSPlayer.process (GenericPlayers.py:198-200)
+                self.policy[off:off + n] = 1 / self.engine.A; self.value[off:off + n] = 0
+            elif n:
                 x = self.obs[off:off + n]
                 p, v = (self.nnets[mi]._hip.forward_nhwc8(x, key=100 + mi) if self.nhwc8 else self.nnets[mi].process(x))
                 self.policy[off:off + n] = p; self.value[off:off + n] = v
@@ -401,11 +418,19 @@ class ArenaRunner:
         HipResNet.forward_models([n._hip for n in self.nnets], self.obs, self.policy, self.value, rpm)    # one launch
         e.backup(self.policy, self.value, row_of_slot)
 
+    def _search_wide(self, sims):
+        HipResNet.search_arena_wide([None if n is None else n._hip for n in self.nnets], self.engine, sims,
+                                    None if self.slot_seats is not None else self.player_to_index, self.slot_seats)
+
     def _round_device_split(self, sims):
         """A whole move: the mover of every game -- hence the row <-> game map and the per-model split -- is fixed until
         advance, so the rows are laid out once; then select, and per simulation ONE tower launch for all models plus one
         tree launch (backup k + select k + 1); advance."""
         e = self.engine
+        if self.wide_search:
+            self._search_wide(sims)
+            e.advance(record_history=False)
+            return
         if self.fused_search:
             HipResNet.search_arena([n._hip for n in self.nnets], e, sims, None if self.slot_seats is not None else self.player_to_index, self.slot_seats)
             e.advance(record_history=False)
@@ -422,9 +447,12 @@ class ArenaRunner:
         e.advance(record_history=False)
 
     def capture(self):
-        """Capture one whole round (all simulations of a move + advance) as a hipGraph (device-side split only)."""
-        assert self.device_split
-        self._step_device_split()                                    # warm: lazy allocations happen outside the capture
+        """Capture one whole round (all simulations of a move + advance) as a hipGraph (device-side split or a persistent launch)."""
+        assert self.device_split or self.wide_search
+        if self.wide_search:
+            self._search_wide(0)                                     # one-time set-up outside the capture
+        else:
+            self._step_device_split()                                # warm: lazy allocations happen outside the capture
         if self.fused_search:
             HipResNet.search_arena([n._hip for n in self.nnets], self.engine, 0, None if self.slot_seats is not None else self.player_to_index, self.slot_seats)
         self.engine.reset()                                          # (the warm step is not part of any game)
@@ -435,7 +463,7 @@ class ArenaRunner:
         self._graph = g
 
     def play_round(self, eager=False):
-        if self.device_split and (self._graph is not None or self.fused_search):
+        if self.wide_search or (self.device_split and (self._graph is not None or self.fused_search)):
             if eager or self._graph is None:
                 self._round_device_split(int(self.args.get('numMCTSSims', 100)))
             else:

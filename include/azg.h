@@ -399,6 +399,20 @@ int  azg_search_arena_f16(azg_engine *e, void *stream, int nmodels, const void *
                           const float *const *pre_scale_dev, const float *const *pre_shift_dev, int nblocks, const void *const *head_w_packed_dev,
                           const float *const *head_b_dev, const int32_t *p2i_host, const uint32_t *seat_of_slot_dev, int sims);
 
+/* The same for factorised-head networks (the pairs of azg_search_wide_exact_f16: brandubh x 64, the 3-player env x 32, connect4 x {32, 64},
+ * othello x {32, 64}) on arena engines: one game per workgroup, `sims` x [find_leaf on the MOVER's tree, the MOVER's model -- tower, 1x1
+ * head convolutions and ALL A + P+1 logits, what NNetWrapper.process returns --, process_results].  Model m's parameters as
+ * azg_search_wide_exact_f16 takes them, in entry m of each array.  A model whose pointers are ALL null is a raw seat (RawMCTSPlayer.process:
+ * policy float32(1 / A) for every action, value zeros; no network runs for its games).  Seating as azg_search_arena_f16.  Results identical
+ * to `sims` x [azg_select / the models' NNetWrapper.process on the rows of azg_arena_rows / azg_backup].  sims == 0: one-time setup only.
+ * AZG_E_UNSUPPORTED: a self-play engine or another (game, channels); AZG_E_INVALID_ARG: nmodels outside [num_players, 4], a model with only
+ * some of its pointers null, a bad feat_k. */
+int  azg_search_arena_wide_exact_f16(azg_engine *e, void *stream, int nmodels, const void *const *w_packed_dev, const float *const *bias_dev,
+                                     const float *const *pre_scale_dev, const float *const *pre_shift_dev, int nblocks, int channels,
+                                     const void *const *head1_w_packed_dev, const float *const *head1_b_dev, const void *const *wps_packed_dev,
+                                     const void *const *wv_packed_dev, const float *const *head_b_dev, int feat_k, const int32_t *p2i_host,
+                                     const uint32_t *seat_of_slot_dev, int sims);
+
 /* Observation planes as callers of the reference hold them -- f32 [boards][C][H*W] (GameState.observation, the batch tensors of
  * Coach.py:294-300) -- into the tower's input rows [boards * H*W][8] fp16 (channels padded to 8), one launch.  obs_dev may be device
  * memory or page-locked host memory the device can read (a registered shared batch tensor: the H2D and the conversion are then one pass). */
