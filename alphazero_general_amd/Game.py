@@ -112,7 +112,7 @@ class GameState:
         raise NotImplementedError('Symmetries not implemented for this environment. Set symmetricSamples to False in args.')
 
 
-_REFERENCE_ENVS = {'envs.connect4.connect4': 0, 'envs.brandubh.fastafl': 1, 'envs.othello.othello': 3}
+_REFERENCE_ENVS = {'envs.connect4.connect4': 0, 'envs.brandubh.fastafl': 1, 'envs.othello.othello': 3, 'envs.gobang.gobang': 4}
 
 
 def azg_game_id(game_cls_or_state):

@@ -32,6 +32,8 @@ def encode_state(gs):
         return np.asarray(gs._board._state, np.int8).reshape(-1), gs.player, gs.turns, int(gs._board._king_captured)
     if gid == 3:                   # the reference's own othello Game (envs/othello/othello.pyx:17-41): pieces[x][y] -> cells[8x + y]
         return np.asarray(gs._board.pieces, np.int8).reshape(-1), gs.player, gs.turns
+    if gid == 4:                   # the reference's own gobang Game (envs/gobang/gobang.pyx:41-50): pieces[x][y] -> cells[15x + y]
+        return np.asarray(gs._board.pieces, np.int8).reshape(-1), gs.player, gs.turns
     raise NotImplementedError('cannot encode %r for the device engine' % type(gs))
 
 
@@ -265,7 +267,7 @@ class MCTS:
     @staticmethod
     def _persistent_net(nn, e):
         """the HipResNet behind `nn` if nn is an NNetWrapper (or its bound predict / __call__) whose network has a persistent search
-        launch for this engine's game on this engine's device, else None"""
+        launch for this engine's game on this engine's device and that launch is the faster form (HipResNet.search_preferred), else None"""
         from .nnet import NNetWrapper
         w = nn if isinstance(nn, NNetWrapper) else getattr(nn, '__self__', None)
         if not isinstance(w, NNetWrapper) or not w.fast or w.device.type != 'cuda' or w.device.index not in (None, e.device.index):
@@ -273,7 +275,7 @@ class MCTS:
         if w._infer is None:
             w.refresh()
         hip = w._hip
-        return hip if (hip is not None and hip.can_search and hip.game == e.game) else None
+        return hip if (hip is not None and hip.search_preferred and hip.game == e.game) else None
 
     def raw_search(self, gs, sims, add_root_noise, add_root_temp):     # MCTS.pyx:175-183
         ref = self._fallback(gs)

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('AZG_LIB_PATH') or os.path.join(HERE, 'lib', 'libazg_hip.so')   # (override: measurement builds)
 ABI_VERSION = 7
 
-GAME_CONNECT4, GAME_BRANDUBH, GAME_TRIMOK, GAME_OTHELLO = 0, 1, 2, 3
+GAME_CONNECT4, GAME_BRANDUBH, GAME_TRIMOK, GAME_OTHELLO, GAME_GOBANG = 0, 1, 2, 3, 4
 E_INVALID_ARG, E_HIP, E_INVALID_ACTION, E_TREE_FULL, E_EXAMPLES_FULL, E_UNSUPPORTED, E_INTERNAL, E_FLOATING_POINT = -1, -2, -3, -4, -5, -6, -7, -8
 ERROR_NAMES = {-1: 'AZG_E_INVALID_ARG', -2: 'AZG_E_HIP', -3: 'AZG_E_INVALID_ACTION', -4: 'AZG_E_TREE_FULL',
                -5: 'AZG_E_EXAMPLES_FULL', -6: 'AZG_E_UNSUPPORTED', -7: 'AZG_E_INTERNAL', -8: 'AZG_E_FLOATING_POINT'}
@@ -169,3 +169,38 @@ def states_array(n):
 
 def state_to_np(s, cells):
     return np.frombuffer(bytes(s.cells), dtype=np.int8)[:cells].copy()
+
+
+# gobang's azg_state.cells (include/azg.h): two packed 256-bit boards, colour 1 then colour -1, bit 16x + y = pieces[x][y]
+GOBANG_N = 15
+
+
+def gobang_pack(cells):
+    """225 int8 cells (cells[15x + y] = pieces[x][y]) -> the 64 bytes of azg_state.cells"""
+    b = np.asarray(cells, np.int8).reshape(GOBANG_N, GOBANG_N)
+    out = np.zeros(64, np.uint8)
+    for i, colour in enumerate((1, -1)):
+        bits = np.zeros((16, 16), np.uint8)
+        bits[:GOBANG_N, :GOBANG_N] = b == colour
+        out[32 * i:32 * (i + 1)] = np.packbits(bits.reshape(-1), bitorder='little')
+    return out.view(np.int8)
+
+
+def gobang_unpack(raw):
+    """the 64 bytes of azg_state.cells -> 225 int8 cells"""
+    raw = np.frombuffer(bytes(raw), np.uint8)
+    out = np.zeros((GOBANG_N, GOBANG_N), np.int8)
+    for i, colour in enumerate((1, -1)):
+        bits = np.unpackbits(raw[32 * i:32 * (i + 1)], bitorder='little').reshape(16, 16)[:GOBANG_N, :GOBANG_N]
+        out[bits != 0] = colour
+    return out.reshape(-1)
+
+
+def cells_to_state(game, cells):
+    """a board as Python callers hold it -> the int8 array that goes into azg_state.cells (at most 64 entries)"""
+    return gobang_pack(cells) if game == GAME_GOBANG else np.asarray(cells, np.int8).reshape(-1)
+
+
+def state_cells(s, game, cells):
+    """azg_state.cells -> the board as Python callers hold it (`cells` entries)"""
+    return gobang_unpack(bytes(s.cells)) if game == GAME_GOBANG else state_to_np(s, cells)

@@ -494,13 +494,13 @@ template <class G, int HW, bool COMPACT = false> struct WideScratch {
                          // SNAP: the header and the tape counter as the walker LEFT them at the end of its tree phase (overlapped one-game
                          // tile, wide_overlap_nw: the other wavefronts of the game enter the next tree phase long after the walker has --
                          // the helper only when the walker may have FINISHED it, so two copies take turns: phase s writes copy s & 1)
-                         SNAP = (MAIL + (COMPACT ? 0 : (int)sizeof(WalkMail)) + 15) / 16 * 16, SNAP_BYTES = 80,
+                         SNAP = (MAIL + (COMPACT ? 0 : (int)sizeof(WalkMailOf<G>)) + 15) / 16 * 16, SNAP_BYTES = 80,
                          BYTES = (SNAP + ((COMPACT || AZG_OVL_NW == 0) ? 0 : 2 * SNAP_BYTES) + 15) / 16 * 16;
 };
 // all of the wide search mode's LDS behind the image: the per-game scratch, an error word, and the value head's P + 1 weight rows
 // + biases (the same for every game and simulation: fetched once per launch instead of once per simulation by every walker;
 // COMPACT: they stay in global memory)
-template <class G> struct WideMailFits { static_assert(G::MAX_TURNS + 2 <= 128, "WalkMail::act holds one action per level of a find_leaf path"); };
+template <class G> struct WideMailFits { static_assert(G::MAX_TURNS + 2 <= (int)(sizeof(WalkMailOf<G>::act) / sizeof(int)), "WalkMail::act holds one action per level of a find_leaf path"); };
 template <class G, int HW, int BOARDS, bool COMPACT = false> struct WideLds : WideMailFits<G> {
     static constexpr int NV = G::P + 1, FK = WideScratch<G, HW, COMPACT>::FK;
     // (ZERO: a feature row of zeros -- the A-operand rows of heads_full_lds that no board stands behind; zeroed once per launch)
@@ -892,7 +892,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
             // (and the fourth one runs the game rules one level behind the walk: WalkMail, azg_kernels.h)
             constexpr bool RULES_WAVE = NT / 64 >= 4 * BOARDS;
             const bool livegame = slot < sa.ev.B && role < (SOLO ? 1 : RULES_WAVE ? 4 : MASK_WAVE ? 3 : 2);
-            [[maybe_unused]] WalkMail *mail = reinterpret_cast<WalkMail *>(ws + WS::MAIL);
+            [[maybe_unused]] WalkMailOf<G> *mail = reinterpret_cast<WalkMailOf<G> *>(ws + WS::MAIL);
             const int tree = IS_WARENA ? slot * sa.ev.T + (wsel & 15) : slot;   // (self-play: one tree per slot; arena: the mover's, tree_of_slot)
             // The tree functions reach the header, the path, the tape counter, the tallies and the root state through the View's
             // pointers: here those point into the game's LDS scratch (offset so that [tree] / [slot] lands on it), so that every
@@ -937,7 +937,14 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
             const bool has_policy = livegame && sim > 0 && !hr.leaf_e && hr.leaf_fc >= 0;
             const bool root_noise = has_policy && hr.leaf == LEAF_IS_ROOT && sa.ev.add_noise;
             auto sink = [&](const typename G::S &ls, int ln) {       // leaf observation -> the image rows of board bd (32 stem channels)
-                if (ln < HW) {
+                if constexpr (HW > 64) {                             // (a board of more than 64 cells: each lane writes every 64th row)
+                    for (int c = ln; c < HW; c += 64) {
+                        char *row = img + GEO::qrow(bd * HW + c) * RS;
+                        *reinterpret_cast<half8 *>(row) = G::obs8(ls, c);
+                        const uint4 z = make_uint4(0, 0, 0, 0);
+                        *reinterpret_cast<uint4 *>(row + 16) = z; *reinterpret_cast<uint4 *>(row + 32) = z; *reinterpret_cast<uint4 *>(row + 48) = z;
+                    }
+                } else if (ln < HW) {
                     char *row = img + GEO::qrow(bd * HW + ln) * RS;
                     *reinterpret_cast<half8 *>(row) = G::obs8(ls, ln);
                     const uint4 z = make_uint4(0, 0, 0, 0);
@@ -1066,10 +1073,19 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
                 if (P.dbg && wave == BOARDS && lane == 0 && blockIdx.x < 512 && sim >= 8 && has_policy) P.dbg[2048 + 4096 * 5 + (size_t)blockIdx.x * 8 + 5] += 1;
 #endif
             } else if (role == 0 && lane < HW) {                     // no game behind this board: zero planes
-                char *row = img + GEO::qrow(bd * HW + lane) * RS;
-                const uint4 z = make_uint4(0, 0, 0, 0);
-                *reinterpret_cast<uint4 *>(row) = z; *reinterpret_cast<uint4 *>(row + 16) = z;
-                *reinterpret_cast<uint4 *>(row + 32) = z; *reinterpret_cast<uint4 *>(row + 48) = z;
+                if constexpr (HW > 64) {                             // (every 64th row per lane)
+                    for (int c = lane; c < HW; c += 64) {
+                        char *row = img + GEO::qrow(bd * HW + c) * RS;
+                        const uint4 z = make_uint4(0, 0, 0, 0);
+                        *reinterpret_cast<uint4 *>(row) = z; *reinterpret_cast<uint4 *>(row + 16) = z;
+                        *reinterpret_cast<uint4 *>(row + 32) = z; *reinterpret_cast<uint4 *>(row + 48) = z;
+                    }
+                } else {
+                    char *row = img + GEO::qrow(bd * HW + lane) * RS;
+                    const uint4 z = make_uint4(0, 0, 0, 0);
+                    *reinterpret_cast<uint4 *>(row) = z; *reinterpret_cast<uint4 *>(row + 16) = z;
+                    *reinterpret_cast<uint4 *>(row + 32) = z; *reinterpret_cast<uint4 *>(row + 48) = z;
+                }
             }
             if (sim == sa.sims) break;                           // the last backup is done: no evaluation follows
             AZG_WPHASE(1);

@@ -49,8 +49,9 @@ static const azg_game_info k_info[] = {
     {BR::A, BR::OBS_C, BR::H, BR::W, BR::P, BR::HAS_DRAW, BR::MAX_TURNS, BR::NSYM, BR::CELLS, BR::MAXK},
     {TM::A, TM::OBS_C, TM::H, TM::W, TM::P, TM::HAS_DRAW, TM::MAX_TURNS, TM::NSYM, TM::CELLS, TM::MAXK},
     {OT::A, OT::OBS_C, OT::H, OT::W, OT::P, OT::HAS_DRAW, OT::MAX_TURNS, OT::NSYM, OT::CELLS, OT::MAXK},
+    {GB::A, GB::OBS_C, GB::H, GB::W, GB::P, GB::HAS_DRAW, GB::MAX_TURNS, GB::NSYM, GB::CELLS, GB::MAXK},
 };
-static const int k_num_games = 4;
+static const int k_num_games = 5;
 
 extern "C" int azg_abi_version(void) { return AZG_ABI_VERSION; }
 #ifndef AZG_SRC_SHA
@@ -96,6 +97,17 @@ template <typename T> static int dalloc(azg_engine *e, T **p, size_t count) {
     case AZG_GAME_BRANDUBH: { using G = BR; CALL; } break; \
     case AZG_GAME_TRIMOK: { using G = TM; CALL; } break; \
     case AZG_GAME_OTHELLO: { using G = OT; CALL; } break; \
+    case AZG_GAME_GOBANG: { using G = GB; CALL; } break; \
+    default: return fail(AZG_E_UNSUPPORTED, "game has no device rules"); }
+// the same for the sparse heads (head features -> logits of the leaf's children only): not built for gobang, where nearly every
+// cell is a legal move, so a sparse row saves little and the 3616-wide feature dot products would spill
+#define SPARSE_GAME_SWITCH(e, CALL) \
+    switch ((e)->cfg.game) { \
+    case AZG_GAME_CONNECT4: { using G = C4; CALL; } break; \
+    case AZG_GAME_BRANDUBH: { using G = BR; CALL; } break; \
+    case AZG_GAME_TRIMOK: { using G = TM; CALL; } break; \
+    case AZG_GAME_OTHELLO: { using G = OT; CALL; } break; \
+    case AZG_GAME_GOBANG: return fail(AZG_E_UNSUPPORTED, "no sparse heads for gobang (use the dense heads)"); \
     default: return fail(AZG_E_UNSUPPORTED, "game has no device rules"); }
 
 static void prof_begin(azg_engine *e, hipStream_t s, int fam, EvPair &p) {
@@ -351,13 +363,13 @@ extern "C" int azg_backup_select_features(azg_engine *e, void *stream, const voi
     if (flags >= 0) { v.add_noise = (flags & AZG_FLAG_NOISE) ? 1 : 0; v.add_temp = (flags & AZG_FLAG_TEMP) ? 1 : 0; }
     const HeadRows hd{(const _Float16 *)head_rows, head_b, feat_k};
     int want = 0;
-    GAME_SWITCH(e, want = head_fk<G>());
+    SPARSE_GAME_SWITCH(e, want = head_fk<G>());
     if (feat_k != want) return fail(AZG_E_INVALID_ARG, "feat_k must be cells x 16 rounded up to a multiple of 32 for this game");
     EvPair p; prof_begin(e, s, 1, p);
     const float *nov = nullptr, *f = (const float *)feat;
-    if (obs_dtype == 0) { GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, float, false, IN_FEATURES>), dim3(v.B), dim3(128), 0, s, v, f, nov, 0, (float *)obs, row_of_slot, do_select, hd)); }
-    else if (obs_dtype == 1) { GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, _Float16, false, IN_FEATURES>), dim3(v.B), dim3(128), 0, s, v, f, nov, 0, (_Float16 *)obs, row_of_slot, do_select, hd)); }
-    else { GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, _Float16, true, IN_FEATURES>), dim3(v.B), dim3(128), 0, s, v, f, nov, 0, (_Float16 *)obs, row_of_slot, do_select, hd)); }
+    if (obs_dtype == 0) { SPARSE_GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, float, false, IN_FEATURES>), dim3(v.B), dim3(128), 0, s, v, f, nov, 0, (float *)obs, row_of_slot, do_select, hd)); }
+    else if (obs_dtype == 1) { SPARSE_GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, _Float16, false, IN_FEATURES>), dim3(v.B), dim3(128), 0, s, v, f, nov, 0, (_Float16 *)obs, row_of_slot, do_select, hd)); }
+    else { SPARSE_GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, _Float16, true, IN_FEATURES>), dim3(v.B), dim3(128), 0, s, v, f, nov, 0, (_Float16 *)obs, row_of_slot, do_select, hd)); }
     prof_end(e, s, 1, p);
     HIPCHK(hipGetLastError());
     return AZG_OK;
@@ -369,10 +381,10 @@ extern "C" int azg_leaf_heads_sparse_f16(azg_engine *e, void *stream, const void
     if (logits_stride < e->gi.action_size + e->gi.num_players + 1 || e->gi.action_size > 1024)
         return fail(AZG_E_INVALID_ARG, "logits_stride must hold A + P + 1 logits (A <= 1024)");
     int want = 0;
-    GAME_SWITCH(e, want = head_fk<G>());
+    SPARSE_GAME_SWITCH(e, want = head_fk<G>());
     if (feat_k != want) return fail(AZG_E_INVALID_ARG, "feat_k must be cells x 16 rounded up to a multiple of 32 for this game");
     const HeadRows hd{(const _Float16 *)head_rows, head_b, feat_k};
-    GAME_SWITCH(e, hipLaunchKernelGGL((k_leaf_heads_sparse<G>), dim3(e->v.B), dim3(64), 0, (hipStream_t)stream, e->v, (const _Float16 *)feat, hd,
+    SPARSE_GAME_SWITCH(e, hipLaunchKernelGGL((k_leaf_heads_sparse<G>), dim3(e->v.B), dim3(64), 0, (hipStream_t)stream, e->v, (const _Float16 *)feat, hd,
                                       row_of_slot, logits, logits_stride));
     HIPCHK(hipGetLastError());
     return AZG_OK;
@@ -1014,7 +1026,12 @@ static int dispatch_tower(hipStream_t s, int game, int channels, const TowerPara
         if (sp == 2) return launch_tower<OT::H, OT::W, 2, 64, 2>(s, P);
         return launch_tower<OT::H, OT::W, 2, 64>(s, P);
     }
-    return fail(AZG_E_UNSUPPORTED, "no MFMA tower for this game / channel count (supported: connect4 x {32,64,128}, brandubh x {64,128}, trimok x 32, othello x {32,64} channels)");
+    // gobang: a 15x15 board is 225 pixels, 15 pixel subtiles (15 spare lanes, five border classes) -- an odd count, so no k-split; one
+    // board per tile, its subtiles dealt to three pixel groups of five (every width: 3, 6 or 12 waves)
+    if (game == AZG_GAME_GOBANG && channels == 32) return launch_tower<GB::H, GB::W, 1, 32, 3>(s, P);
+    if (game == AZG_GAME_GOBANG && channels == 64) return launch_tower<GB::H, GB::W, 1, 64, 3>(s, P);
+    if (game == AZG_GAME_GOBANG && channels == 128) return launch_tower<GB::H, GB::W, 1, 128, 3>(s, P);
+    return fail(AZG_E_UNSUPPORTED, "no MFMA tower for this game / channel count (supported: connect4 x {32,64,128}, brandubh x {64,128}, trimok x 32, othello x {32,64}, gobang x {32,64,128} channels)");
 }
 
 // [boards, C, H*W] f32 planes (what GameState.observation / the reference's batch tensors hold) -> the tower's input rows [boards * H*W][8] fp16
@@ -1193,12 +1210,20 @@ static int wide_tile_launch(azg_engine *e, hipStream_t s, const TowerParams &P, 
         if (bt == 2) return launch_tower<OT::H, OT::W, 2, 64, 2, SW>(s, P, sa, init, occ);
         if (bt == 3) return launch_tower<OT::H, OT::W, 3, 64, 2, SW>(s, P, sa, init, occ);
         if (bt == 4) return launch_tower<OT::H, OT::W, 4, 64, 2, SW>(s, P, sa, init, occ);
+    } else if (game == AZG_GAME_GOBANG && (channels == 32 || channels == 64)) {
+        // the one-game tile of the stand-alone 15x15 towers (three pixel groups of five subtiles; walker, helper, mask wave and, at 64
+        // channels, the rules wave); exact heads only -- gobang has no sparse heads
+        if constexpr (EXACT) {
+            if (bt == 1 && channels == 32) return launch_tower<GB::H, GB::W, 1, 32, 3, SearchWide<GB, 1, EXACT>>(s, P, SearchWide<GB, 1, EXACT>{e->v, sims, hd, hf}, init, occ);
+            if (bt == 1 && channels == 64) return launch_tower<GB::H, GB::W, 1, 64, 3, SearchWide<GB, 1, EXACT>>(s, P, SearchWide<GB, 1, EXACT>{e->v, sims, hd, hf}, init, occ);
+        }
     }
     return AZG_E_UNSUPPORTED;
 }
 
 static int wide_max_tile(int game, int channels) {
     if ((game == AZG_GAME_BRANDUBH || game == AZG_GAME_OTHELLO) && channels == 64) return 4;
+    if (game == AZG_GAME_GOBANG && (channels == 32 || channels == 64)) return 1;
     if ((game == AZG_GAME_TRIMOK && channels == 32) || (game == AZG_GAME_CONNECT4 && (channels == 32 || channels == 64)) || (game == AZG_GAME_OTHELLO && channels == 32)) return 2;
     return 0;
 }
@@ -1349,7 +1374,8 @@ static int search_wide(azg_engine *e, void *stream, const void *w, const float *
     const int A = e->gi.action_size, NV = e->gi.num_players + 1, hw = e->gi.obs_h * e->gi.obs_w;
     if (feat_k != (hw * 16 + 31) / 32 * 32) return fail(AZG_E_INVALID_ARG, "feat_k must be H*W*16 rounded up to 32");
     if (wide_max_tile(e->cfg.game, channels) == 0)
-        return fail(AZG_E_UNSUPPORTED, "persistent wide-head search: brandubh x 64, the 3-player env x 32, connect4 x {32, 64} and othello x {32, 64} channels (use azg_select / network / azg_backup)");
+        return fail(AZG_E_UNSUPPORTED, "persistent wide-head search: brandubh x 64, the 3-player env x 32, connect4 x {32, 64}, othello x {32, 64} and gobang x {32, 64} channels (use azg_select / network / azg_backup)");
+    if (!EXACT && e->cfg.game == AZG_GAME_GOBANG) return fail(AZG_E_UNSUPPORTED, "no sparse heads for gobang (use the exact persistent launch)");
     TowerParams P{nullptr, w, bias, pre_scale, pre_shift, nullptr, e->v.B, nblocks, nullptr, nullptr, nullptr, nullptr, A, NV, nullptr, head1_w, head1_b, nullptr, feat_k,
                   nullptr, 0, {}};
     hipStream_t s = (hipStream_t)stream;
@@ -1423,7 +1449,7 @@ extern "C" int azg_search_arena_wide_exact_f16(azg_engine *e, void *stream, int 
     const int game = e->cfg.game;
     if (!e->v.arena || wide_max_tile(game, channels) == 0)
         return fail(AZG_E_UNSUPPORTED, "the persistent wide arena launch is built for arena engines on brandubh x 64, the 3-player env x 32, connect4 x {32, 64} "
-                                       "and othello x {32, 64} channels (use azg_select / network / azg_backup)");
+                                       "othello x {32, 64} and gobang x {32, 64} channels (use azg_select / network / azg_backup)");
     if (nmodels < e->gi.num_players || nmodels > 4) return fail(AZG_E_INVALID_ARG, "one model per player, at most 4");
     const int A = e->gi.action_size, NV = e->gi.num_players + 1, hw = e->gi.obs_h * e->gi.obs_w;
     if (feat_k != (hw * 16 + 31) / 32 * 32) return fail(AZG_E_INVALID_ARG, "feat_k must be H*W*16 rounded up to 32");
@@ -1459,6 +1485,8 @@ extern "C" int azg_search_arena_wide_exact_f16(azg_engine *e, void *stream, int 
     else if (game == AZG_GAME_CONNECT4 && channels == 64) r = wide_arena_tile<C4, 64, 2, 2, 1>(s, P, sa0, init);
     else if (game == AZG_GAME_OTHELLO && channels == 32) r = wide_arena_tile<OT, 32, 2, 1, 1>(s, P, sa0, init);
     else if (game == AZG_GAME_OTHELLO && channels == 64) r = wide_arena_tile<OT, 64, 1, 2, 2>(s, P, sa0, init);
+    else if (game == AZG_GAME_GOBANG && channels == 32) r = wide_arena_tile<GB, 32, 3, 1, 1>(s, P, sa0, init);
+    else if (game == AZG_GAME_GOBANG && channels == 64) r = wide_arena_tile<GB, 64, 3, 1, 1>(s, P, sa0, init);
     if (r == AZG_E_UNSUPPORTED) { g_kev = nullptr; return fail(r, "persistent wide arena launch: no tile for this game / width"); }
     if (!init) netprof_end(s, 2, prof, ep);
     return r;
@@ -1531,6 +1559,7 @@ extern "C" int azg_tower_layout(int game, int boards_per_tile, int channels, int
     AZG_LAYOUT(BR, 1, 64); AZG_LAYOUT(BR, 2, 64); AZG_LAYOUT(BR, 2, 128);
     AZG_LAYOUT(TM, 2, 32); AZG_LAYOUT(TM, 5, 32);
     AZG_LAYOUT(OT, 1, 32); AZG_LAYOUT(OT, 2, 32); AZG_LAYOUT(OT, 4, 32); AZG_LAYOUT(OT, 1, 64); AZG_LAYOUT(OT, 2, 64); AZG_LAYOUT(OT, 3, 64); AZG_LAYOUT(OT, 4, 64);
+    AZG_LAYOUT(GB, 1, 32); AZG_LAYOUT(GB, 1, 64); AZG_LAYOUT(GB, 1, 128);
 #undef AZG_LAYOUT
     return fail(AZG_E_UNSUPPORTED, "no tower instantiation for this (game, boards per tile, channels)");
 }

@@ -551,4 +551,173 @@ struct OT {
     }
 };
 
+
+// ================================================================================================ gobang
+// alphazero/envs/gobang/gobang.pyx + GobangLogic.pyx: 15x15, five in a row.  Cell i = 15x + y of the reference's pieces[x][y] (action a
+// places a stone on cell a, every empty cell is legal), colour 1 for player 0 and -1 for player 1.  The first board that one wavefront
+// cannot hold a cell per lane: each colour is a 256-bit bitboard of four 64-bit words in SGPRs, 15 rows of 16 bits (bit 16x + y; bit 15
+// of every row and the 16 bits behind row 14 stay zero), so a run shifted along any of the four directions never wraps onto the next
+// row.  The observation, legal-move list and symmetries walk the cells in chunks of 64 (cell c = lane + 64 j).
+struct GB {
+    static constexpr int ID = AZG_GAME_GOBANG;
+    static constexpr int A = 225, H = 15, W = 15, CELLS = 225, P = 2, HAS_DRAW = 1, MAX_TURNS = 225, NSYM = 8;
+    static constexpr int OBS_C = 4, OBS = OBS_C * CELLS, MAXK = 225;     // every empty cell is legal
+    static constexpr int SYM_RAW = 7;                                    // the identity is the LAST entry of symmetries(), as othello
+    static constexpr uint64_t ROWS4 = 0x7FFF7FFF7FFF7FFFULL, ROWS3 = 0x00007FFF7FFF7FFFULL;     // the board's bits of words 0-2 / 3
+    struct S { uint64_t b0[4], b1[4]; int player, turns; };              // b0: colour 1 (player 0), b1: colour -1
+
+    static AZG_DEV int bit_of(int i) { return (i / 15) * 16 + i % 15; }  // cell -> packed bit
+    static AZG_DEV uint64_t word(const uint64_t (&b)[4], int w) { return w == 0 ? b[0] : w == 1 ? b[1] : w == 2 ? b[2] : b[3]; }
+    static AZG_DEV int bit(const uint64_t (&b)[4], int p) { return (int)((word(b, p >> 6) >> (p & 63)) & 1); }
+    static AZG_DEV uint64_t rows(int w) { return w == 3 ? ROWS3 : ROWS4; }
+    static AZG_DEV S load(const azg_state *st, int lane) {               // (azg.h: two packed boards in cells[64])
+        (void)lane;
+        const uint32_t *q = reinterpret_cast<const uint32_t *>(st->cells);
+        S s;
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            s.b0[w] = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)q[2 * w + 1]) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)q[2 * w]);
+            s.b1[w] = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)q[9 + 2 * w]) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)q[8 + 2 * w]);
+        }
+        s.player = __builtin_amdgcn_readfirstlane(st->player);
+        s.turns = __builtin_amdgcn_readfirstlane(st->turns);
+        return s;
+    }
+    static AZG_DEV void init(S &s) {
+#pragma unroll
+        for (int w = 0; w < 4; w++) { s.b0[w] = 0; s.b1[w] = 0; }
+        s.player = 0; s.turns = 0;
+    }
+    static AZG_DEV int cell(const S &s, int i) { const int p = bit_of(i); return bit(s.b0, p) - bit(s.b1, p); }
+    static AZG_DEV void store(const S &s, azg_state *st, int lane) {     // lane j < 16 writes 32-bit word j of the two boards
+        if (lane < 16) {
+            const int w = (lane >> 1) & 3;
+            const uint64_t v = lane < 8 ? word(s.b0, w) : word(s.b1, w);
+            reinterpret_cast<uint32_t *>(st->cells)[lane] = (lane & 1) ? (uint32_t)(v >> 32) : (uint32_t)v;
+        }
+        if (lane == 0) { st->player = s.player; st->turns = s.turns; st->aux[0] = 0; st->aux[1] = 0; }
+    }
+    static AZG_DEV void play(S &s, int a) {                              // execute_move (GobangLogic.pyx:94-99)
+        const int p = bit_of(__builtin_amdgcn_readfirstlane(a));
+        const uint64_t m = 1ULL << (p & 63);
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            if (w == (p >> 6)) { if (s.player == 0) s.b0[w] |= m; else s.b1[w] |= m; }
+        }
+        s.player ^= 1; s.turns += 1;
+    }
+    // the 256-bit board shifted towards bit 0 by d < 64 bits: bit q of the result is bit q + d of b
+    static AZG_DEV void shr(const uint64_t (&b)[4], int d, uint64_t (&o)[4]) {
+#pragma unroll
+        for (int w = 0; w < 4; w++) o[w] = (b[w] >> d) | (w < 3 ? b[w + 1] << (64 - d) : 0ULL);
+    }
+    // start cells of a run of five of `b`: bit q is set iff q, q + d, ..., q + 4d all are, for the four steps of get_win_state
+    // (GobangLogic.pyx:66-86): along the first index (+16), the second (+1), the diagonal (+17) and the anti-diagonal (w + l, h - l:
+    // +15).  A run that would leave the board passes a padding bit or a bit behind row 14, which are zero.
+    static AZG_DEV void fives(const uint64_t (&b)[4], uint64_t (&acc)[4]) {
+#pragma unroll
+        for (int w = 0; w < 4; w++) acc[w] = 0;
+        const int steps[4] = {16, 1, 17, 15};
+#pragma unroll
+        for (int di = 0; di < 4; di++) {
+            uint64_t r[4] = {b[0], b[1], b[2], b[3]}, t[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                shr(r, steps[di], t);
+#pragma unroll
+                for (int w = 0; w < 4; w++) r[w] = b[w] & t[w];
+            }
+#pragma unroll
+            for (int w = 0; w < 4; w++) acc[w] |= r[w];
+        }
+    }
+    // win_state (gobang.pyx:133-148, get_win_state): the scan visits start cells (w outer, h inner) in ascending packed-bit order and
+    // the first run it meets decides, so of two colours that both hold a five the one whose earliest start cell is lower wins; no
+    // run and no empty cell: a draw
+    static AZG_DEV int win_bits(const S &s) {
+        uint64_t f0[4], f1[4];
+        fives(s.b0, f0); fives(s.b1, f1);
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const uint64_t m = f0[w] | f1[w];
+            if (m) return (f0[w] & (m & (~m + 1))) ? 1 : 2;
+        }
+        bool full = true;
+#pragma unroll
+        for (int w = 0; w < 4; w++) full = full && (s.b0[w] | s.b1[w]) == rows(w);
+        return full ? 4 : 0;
+    }
+    // child i < k of the list is the i-th empty cell (ascending): the lane of every empty cell stores its cell number at its rank (the
+    // empty cells below it) in act_lds, then lane l reads child c * 64 + l back
+    static AZG_DEV int valid_list(const S &s, int lane, int *act_lds, int (&my_a)[4]) {
+        uint64_t e[4];
+#pragma unroll
+        for (int w = 0; w < 4; w++) e[w] = ~(s.b0[w] | s.b1[w]) & rows(w);
+        const int c0 = __popcll(e[0]), c1 = __popcll(e[1]), c2 = __popcll(e[2]), k = c0 + c1 + c2 + __popcll(e[3]);
+        wave_sync();                                                     // (an earlier list's reads are done)
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const int i = c * 64 + lane;
+            if (i < CELLS) {
+                const int p = bit_of(i), w = p >> 6, b = p & 63;
+                const uint64_t ew = word(e, w);
+                if ((ew >> b) & 1)
+                    act_lds[(w > 0 ? c0 : 0) + (w > 1 ? c1 : 0) + (w > 2 ? c2 : 0) + __popcll(ew & ((1ULL << b) - 1ULL))] = i;
+            }
+        }
+        wave_sync();
+#pragma unroll
+        for (int c = 0; c < 4; c++) my_a[c] = c * 64 + lane < k ? act_lds[c * 64 + lane] : -1;
+        return k;
+    }
+    // observation (gobang.pyx:150-157): pieces == 1, pieces == -1, a plane of `player`, a plane of float32(turns / 225)
+    static AZG_DEV float turn_plane(const S &s) { return (float)((double)s.turns / 225.0); }
+    template <typename OT_> static AZG_DEV void write_obs(const S &s, OT_ *out, int lane) {
+        const float pl = (float)s.player, tn = turn_plane(s);
+        for (int c = lane; c < CELLS; c += 64) {
+            const int p = bit_of(c);
+            out[c] = (OT_)(float)bit(s.b0, p);
+            out[CELLS + c] = (OT_)(float)bit(s.b1, p);
+            out[2 * CELLS + c] = (OT_)pl;
+            out[3 * CELLS + c] = (OT_)tn;
+        }
+    }
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    static AZG_DEV h8 obs8(const S &s, int c) {                          // the row of cell c (any cell, not only the lane's)
+        const int p = bit_of(c);
+        return (h8){(_Float16)(float)bit(s.b0, p), (_Float16)(float)bit(s.b1, p), (_Float16)(float)s.player, (_Float16)turn_plane(s),
+                    (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+    }
+    static AZG_DEV void write_obs_nhwc8(const S &s, _Float16 *out, int lane) {
+        for (int c = lane; c < CELLS; c += 64) *reinterpret_cast<h8 *>(out + c * 8) = obs8(s, c);
+    }
+    // symmetries (gobang.pyx:159-182): entry k = 2(i-1) + (0 if flipped else 1), i = 1..4: fliplr^flip(rot90^i(pieces)), so k = 7 is
+    // the identity.  Word w of the result is built by one ballot: lane l looks up the source of packed bit 64 w + l
+    static AZG_DEV S symmetry(const S &s, int k) {
+        const int lane = threadIdx.x & 63;
+        const int i = k / 2 + 1;
+        S o = s;
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const int p = w * 64 + lane;
+            int r = p >> 4, c = p & 15;
+            const bool on = r < 15 && c < 15;
+            if ((k & 1) == 0) c = 14 - c;
+            for (int t = 0; t < i; t++) { const int nr = c, nc = 14 - r; r = nr; c = nc; }
+            const int src = on ? r * 16 + c : 0;
+            o.b0[w] = __ballot(on && bit(s.b0, src));
+            o.b1[w] = __ballot(on && bit(s.b1, src));
+        }
+        return o;
+    }
+    // where pi[a] lands under symmetry k (the forward maps: rot90 sends (r, c) to (14-c, r), fliplr (r, c) to (r, 14-c))
+    static AZG_DEV int sym_action(int a, int k) {
+        const int i = k / 2 + 1;
+        int r = a / 15, c = a % 15;
+        for (int t = 0; t < i; t++) { const int nr = 14 - c, nc = r; r = nr; c = nc; }
+        if ((k & 1) == 0) c = 14 - c;
+        return r * 15 + c;
+    }
+};
+
 }  // namespace azg

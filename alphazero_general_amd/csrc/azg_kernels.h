@@ -226,11 +226,15 @@ struct NoGate { AZG_DEV bool operator()(int) const { return false; } };
 // (left in act_lds), win state and player to move back for add_children.  Words grow monotonically over the simulations of a launch
 // (gen = simulation number), so nothing is ever reset: cnt = gen * 1024 + actions published, fin = gen * 1024 + 512 * expand + depth,
 // res = gen once k / e / player are valid.  Same arithmetic, same results as the one-wave form.
-struct WalkMail { int cnt, fin, res, k, e, player, pad0, pad1; int act[128]; };
+// act[] holds one action per level of a find_leaf path (at most MAX_TURNS + 2): 128 for every game whose paths fit, sized by the game
+// beyond (gobang: 227 levels)
+template <int N> struct WalkMailN { int cnt, fin, res, k, e, player, pad0, pad1; int act[N]; };
+using WalkMail = WalkMailN<128>;
+template <class G> using WalkMailOf = WalkMailN<(G::MAX_TURNS + 2 <= 128 ? 128 : (G::MAX_TURNS + 2 + 3) / 4 * 4)>;
 AZG_DEV int mail_load(const int *w) { return __hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 AZG_DEV void mail_store(int *w, int v, int lane) { if (lane == 0) __hip_atomic_store(w, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
-template <class G, class Sink>
-AZG_DEV void follow_tree(const View &ev, int slot, typename G::S st, WalkMail *mb, int gen, int lane, int *act_lds, Sink &&sink) {
+template <class G, class Sink, class Mail>
+AZG_DEV void follow_tree(const View &ev, int slot, typename G::S st, Mail *mb, int gen, int lane, int *act_lds, Sink &&sink) {
     constexpr int NCH = (G::MAXK + 63) / 64;
     const int base = gen * 1024;
     int d = 0, fin = -1;
@@ -256,9 +260,9 @@ AZG_DEV void follow_tree(const View &ev, int slot, typename G::S st, WalkMail *m
     G::store(st, &ev.leaf_states[slot], lane);
     sink(st, lane);
 }
-template <class G, class Sink, class Gate, class Ranks>
+template <class G, class Sink, class Gate, class Ranks, class Mail = WalkMail>
 AZG_DEV void select_tree(const View &ev, int slot, int tree, const HdrR &hr, typename G::S st, uint64_t ctr, int lane, int *act_lds,
-                         Sink &&sink, Gate &&gate, Ranks &&ranks, WalkMail *mb = nullptr, int gen = 0) {
+                         Sink &&sink, Gate &&gate, Ranks &&ranks, Mail *mb = nullptr, int gen = 0) {
     constexpr int NCH = (G::MAXK + 63) / 64;
     const bool split = mb != nullptr;                                        // (follow_tree runs the rules: see WalkMail)
     TreeHdr *h = ev.hdr + tree;

@@ -86,7 +86,7 @@ class DeviceEngine:
         arr = _abi.states_array(len(states))
         for s, st in zip(arr, states):
             cells, player, turns = st[0], st[1], st[2]
-            c = np.asarray(cells, np.int8).reshape(-1)
+            c = _abi.cells_to_state(self.game, cells)
             for i, v in enumerate(c):
                 s.cells[i] = int(v)
             s.player, s.turns = int(player), int(turns)
@@ -98,8 +98,8 @@ class DeviceEngine:
         arr = _abi.states_array(count)
         _abi.check(fn(self.h, _stream(), first, count, arr))
         if full:
-            return [(_abi.state_to_np(s, self.gi.cells), s.player, s.turns, s.aux[0]) for s in arr]
-        return [(_abi.state_to_np(s, self.gi.cells), s.player, s.turns) for s in arr]
+            return [(_abi.state_cells(s, self.game, self.gi.cells), s.player, s.turns, s.aux[0]) for s in arr]
+        return [(_abi.state_cells(s, self.game, self.gi.cells), s.player, s.turns) for s in arr]
 
     def get_states(self, first=0, count=None):
         return self._get(self.L.azg_get_states, first, count)

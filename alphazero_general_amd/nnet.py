@@ -20,6 +20,8 @@ BRANDUBH_NET_ARGS = dotdict(num_channels=64, depth=4, value_head_channels=16, po
                             value_dense_layers=[1024, 128], policy_dense_layers=[1024])           # envs/hnefatafl/train_brandubh.py:50-55
 OTHELLO_NET_ARGS = dotdict(num_channels=64, depth=4, value_head_channels=16, policy_head_channels=16,
                            value_dense_layers=[512, 256], policy_dense_layers=[512])             # envs/othello/train.py:25-30
+GOBANG_NET_ARGS = dotdict(num_channels=128, depth=8, value_head_channels=16, policy_head_channels=16,
+                          value_dense_layers=[2048, 128], policy_dense_layers=[2048])           # envs/gobang/train.py:37-43
 
 
 def _mlp(sizes):
@@ -407,8 +409,17 @@ class HipResNet:
     def can_search(self):
         """a persistent search launch exists for this network: connect4 x 128 channels with fused heads (azg_search_f16), or
         factorised heads on brandubh x 64 / the 3-player env x 32 / connect4 x {32, 64} / othello x {32, 64} channels -- the reference's
-        default net (Coach.py:108-116) is the 32-channel one -- (azg_search_wide_exact_f16 / azg_search_wide_f16)."""
-        return (self.fused_head and self.game == 0 and self.CH == 128) or (self.fact_head and (self.game, self.CH) in ((1, 64), (2, 32), (0, 32), (0, 64), (3, 32), (3, 64)))
+        default net (Coach.py:108-116) is the 32-channel one -- (azg_search_wide_exact_f16 / azg_search_wide_f16); gobang x {32, 64}
+        channels with exact heads only (azg_search_wide_exact_f16; its 128 x 8 net is searched launch per phase)."""
+        return (self.fused_head and self.game == 0 and self.CH == 128) or (self.fact_head and (self.game, self.CH) in ((1, 64), (2, 32), (0, 32), (0, 64), (3, 32), (3, 64),
+                                                                                                                    (4, 32), (4, 64)))
+
+    @property
+    def search_preferred(self):
+        """the persistent launch is the faster form, so fused_search=None takes it: every network with one except gobang's, whose persistent
+        launch spills (1-2 KB of scratch per lane: the exact heads' 113 k-steps) and measured 2-100x slower than the launch-per-phase
+        loop at 128-2048 games (profiles/gobang_throughput.json)"""
+        return self.can_search and self.game != 4
 
     def search(self, engine, sims, exact=False):
         """`sims` whole simulations (select -> this network -> backup) on every slot of `engine` in one persistent launch: the
@@ -659,7 +670,8 @@ class NNetWrapper:
         self._infer, self._graph, self._hip = net.eval(), None, None
         use_hip = self.backend == 'hip' or (self.backend == 'auto' and self.device.type == 'cuda'
                                             and (getattr(self.game_cls, 'AZG_GAME_ID', None), self.args.num_channels) in
-                                            ((0, 32), (0, 64), (0, 128), (1, 64), (1, 128), (2, 32), (3, 32), (3, 64)))
+                                            ((0, 32), (0, 64), (0, 128), (1, 64), (1, 128), (2, 32), (3, 32), (3, 64),
+                                             (4, 32), (4, 64), (4, 128)))
         if use_hip:
             self._hip = HipResNet(FoldedResNet(self.nnet).to(self.device), self.game_cls.AZG_GAME_ID, self.device)
         return self

@@ -114,8 +114,8 @@ class SelfPlayRunner:
         self.sims_per_round = []
         # the whole simulation loop of a move as ONE persistent launch where the network has one (azg_search_f16 / azg_search_wide_f16)
         hip = getattr(nnet, '_hip', None) if nnet is not None else None
-        self.fused_search = (fused_search is None or bool(fused_search)) and self.round_graph and not self.warmup \
-            and hip is not None and hip.can_search and self.game == hip.game
+        self.fused_search = (hip.search_preferred if fused_search is None and hip is not None else bool(fused_search)) and self.round_graph \
+            and not self.warmup and hip is not None and hip.can_search and self.game == hip.game
 
     @property
     def obs(self):
@@ -380,7 +380,8 @@ class ArenaRunner:
         can = self.device_split and self.game == 0 and all(n._hip.CH == 128 for n in self.nnets)
         if fused_search and not (can or can_wide):
             raise NotImplementedError('no persistent arena launch for these models / this game')
-        self.wide_search = can_wide and fused_search is not False
+        # (fused_search=None: where the persistent form is the faster one, HipResNet.search_preferred)
+        self.wide_search = can_wide and (bool(fused_search) or (fused_search is None and all(n._hip.search_preferred for n in self.real)))
         self.fused_search = can if fused_search is None else bool(fused_search) and can
         self._graph = None
         if (self.device_split or self.wide_search) and use_graph:

@@ -47,13 +47,18 @@ typedef enum azg_game {
     AZG_GAME_CONNECT4 = 0,      /* alphazero/envs/connect4/connect4.pyx + Connect4Logic.pyx          */
     AZG_GAME_BRANDUBH = 1,      /* alphazero/envs/brandubh/fastafl.pyx + fastafl/cengine.pyx         */
     AZG_GAME_TRIMOK = 2,        /* build-defined 3-player env (N-player path, BASELINE config 5)     */
-    AZG_GAME_OTHELLO = 3        /* alphazero/envs/othello/othello.pyx + OthelloLogic.pyx (ABI v7)    */
+    AZG_GAME_OTHELLO = 3,       /* alphazero/envs/othello/othello.pyx + OthelloLogic.pyx (ABI v7)    */
+    AZG_GAME_GOBANG = 4         /* alphazero/envs/gobang/gobang.pyx + GobangLogic.pyx (ABI v7)       */
 } azg_game;
 
 /* Game state as it crosses the ABI (all games): the reference's board array, row-major, one int8 per cell
  * (connect4: 1/-1/0 as Connect4Logic.pyx:34; brandubh: piece codes of fastafl/cengine.pyx:24-32; othello: cells[8x + y] =
  * pieces[x][y] of OthelloLogic.pyx:31-46, 1 = player 0's colour, -1 = player 1's, 0 = empty -- all 64 cells, action a plays cell a),
- * GameState._player / _turns (Game.py:10-11) and two game-specific words. */
+ * GameState._player / _turns (Game.py:10-11) and two game-specific words.
+ * Gobang's 15x15 board (225 cells) does not fit one byte per cell: its cells[64] hold two packed boards, 32 bytes each -- colour 1
+ * (player 0) first, then colour -1 (player 1).  A board is four little-endian uint64 words of 15 rows x 16 bits: pieces[x][y]
+ * (action a = 15x + y) is bit 16x + y, bit 15 of every row and bits 240..255 are zero.  aux is zero.  The Python layer
+ * (engine.py) packs and unpacks, so its callers still see 225 int8 cells. */
 typedef struct azg_state {
     int8_t  cells[64];
     int32_t player;

@@ -1,0 +1,432 @@
+"""Gobang on the device (csrc/azg_games.h struct GB, game id 4: the first board of more than 64 cells) against fixtures the REFERENCE
+produced (tests/golden/gb_*.npz, written by tests/golden/make_gobang_goldens.py from alphazero/envs/gobang) and the 15x15 network kernels
+against the fp64 reference of tests/net_reference.py:
+
+  * every gb_rules position through the engine ABI -- random playouts and the hand-built boards (overlines, fives on every edge and
+    corner, full-board draws, both colours holding a five, fours that must not count): valid moves, win state, observation, and
+    play_action by a steered second simulation;
+  * the reference's MCTS (gb_tree: a root with up to 225 children, four chunks of 64) and SelfPlayAgent (gb_agent: plain, root
+    temperature, fastmix -- raw samples with symmetricSamples=False are symmetries()[7]), per-phase and fused launches;
+  * the MCTS class API on envs.gobang.Game against gb_tree;
+  * the tower, head features, logits and probabilities of the 32-, 64- and 128-channel nets, every border class, depths 0 to 6;
+  * NNetWrapper.process on the HIP tower driving the per-phase search; the persistent and sparse-head launches refuse gobang."""
+import os
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+import net_reference as R
+import oracle_lib as ol
+import test_gpu_net_fp64 as F
+import test_gpu_parity as P
+
+pytestmark = pytest.mark.gpu
+G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+GB, DEV, A, NV = 4, 'cuda:0', 225, 3
+NETS = {'gobang_32x4': ('DEFAULT_NET_ARGS', {}), 'gobang_64x4': ('DEFAULT_NET_ARGS', dict(num_channels=64)),
+        'gobang_128x8': ('GOBANG_NET_ARGS', {})}
+
+
+def crc(a):
+    return zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
+
+
+def _game():
+    from alphazero_general_amd.envs.gobang import Game
+    return Game
+
+
+def _states(prefix):
+    Game = _game()
+    out = []
+    for row in prefix:
+        g = Game()
+        for a in row:
+            if a >= 0:
+                g.play_action(int(a))
+        out.append(g.to_azg_state())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------- rules
+def test_gb_rules_vs_reference_tables():
+    from alphazero_general_amd import _abi
+    from alphazero_general_amd.engine import DeviceEngine
+    d = dict(np.load(os.path.join(G, 'gb_rules.npz')))
+    board = np.array([_abi.gobang_unpack(c.tobytes()) for c in d['cells']])
+    n, lens, ws = len(d['lens']), d['lens'], d['ws']
+    assert n >= 10250 and (lens < 0).sum() >= 250
+    eng = DeviceEngine(GB, n, seed=3, sims_hint=4, cpuct=1.25, fpu_reduction=0.2, nodes_per_tree=1024)
+    eng.set_states([(board[i], int(d['player'][i]), int(d['turns'][i])) for i in range(n)])
+    back = eng.get_states()
+    assert all((back[i][0] == board[i]).all() and back[i][1] == d['player'][i] and back[i][2] == d['turns'][i] for i in range(n))
+    obs = eng.new_obs()
+    eng.select(obs)                                           # find_leaf at a fresh root: win_state, valid_moves, add_children, observation
+    o = obs.cpu().numpy()
+    bad = [i for i in range(n) if crc(o[i]) != d['obs_crc'][i]]
+    assert not bad, ('observation', bad[:5])
+    for i in range(n):
+        ch = eng.root_children(i)
+        v = np.zeros(A, np.uint8); v[ch['a']] = 1
+        assert len(ch['a']) == v.sum() and crc(v) == d['valid_crc'][i], ('valid_moves', i)
+        e = eng.tree_info(i)['e']
+        assert e == int(ws[i][0]) + 2 * int(ws[i][1]) + 4 * int(ws[i][2]), ('win_state', i, e, ws[i])
+    # one backup with a policy peaked on the playout's next move, then the second simulation descends exactly that ply
+    nxt = d['next'].astype(np.int64)
+    has_next = (nxt >= 0) & (lens >= 0)
+    has_next[-1] = False
+    pol = np.full((n, A), 1e-4, np.float32)
+    pol[np.arange(n), np.where(has_next, nxt, 0)] = 0.9
+    val = np.full((n, NV), 1.0 / 3, np.float32)
+    eng.backup(torch.from_numpy(pol).to(eng.device), torch.from_numpy(val).to(eng.device))
+    eng.select(obs)
+    o = obs.cpu().numpy()
+    leaves = eng.get_leaf_states()
+    for i in range(n):
+        lc, lp, lt = leaves[i]
+        if ws[i].any():                                       # terminal root: find_leaf stops at it
+            assert len(eng.last_path(i)) == 0 and (lc == board[i]).all(), ('terminal', i)
+            continue
+        if not has_next[i]:
+            continue
+        assert list(eng.last_path(i)) == [nxt[i]], ('descent', i)
+        assert (lc == board[i + 1]).all(), ('play_action: board', i)
+        assert lp == d['player'][i + 1] and lt == d['turns'][i + 1], ('play_action: player / turns', i)
+        assert crc(o[i]) == d['obs_crc'][i + 1], ('observation after play_action', i)
+    eng.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------- tree / agent
+@pytest.mark.parametrize('fixture,cname', [('gb_tree', 'default'), ('gb_tree', 'cpuct4'), ('gb_tree', 'temp'), ('gb_noise_tree', 'noise_temp')])
+def test_gb_tree_vs_reference_goldens(fixture, cname):
+    """gb_noise_tree: root noise over 225 children (four chunks), the reference run with its float32 underflow trap off"""
+    d = dict(np.load(os.path.join(G, fixture + '.npz')))
+    cpuct, fpu, noise, temp, sims = d[cname + '_cfg']
+    noise, temp, sims = bool(noise), bool(temp), int(sims)
+    seed = int(d[cname + '_seed'])
+    R_ = d['prefix'].shape[0]
+    exact = not temp
+    eng = P.engine(game=GB, B=R_, cpuct=cpuct, fpu_reduction=fpu, add_root_noise=noise, add_root_temp=temp, seed=seed, sims_hint=sims)
+    eng.set_states(_states(d['prefix']))
+    obs = eng.new_obs()
+    for s in range(sims):
+        eng.select(obs)
+        for r in range(R_):
+            path = eng.last_path(r)
+            assert len(path) == d[cname + '_depth'][r, s]
+            assert (path[:24] == d[cname + '_paths'][r, s][:len(path)]).all(), (r, s)
+        pol, val = P.fake_batch(torch, seed, range(R_), s, A, NV, eng.device)
+        eng.backup(pol, val)
+        assert (eng.root_counts().cpu().numpy() == d[cname + '_rootn'][:, s]).all(), s
+    kmax = d[cname + '_a'].shape[1]                           # (the fixture keeps the first 128 children of a root in list order)
+    for r in range(R_):
+        ch = eng.root_children(r)
+        k = len(ch['a'])
+        assert k > 64
+        kk = min(k, kmax)
+        assert (ch['a'][:kk] == d[cname + '_a'][r][:kk]).all() and (d[cname + '_a'][r][kk:] == -1).all()
+        assert (ch['n'][:kk] == d[cname + '_n'][r][:kk]).all()
+        for f in ('q', 'p', 'v'):
+            if exact:
+                assert (ch[f][:kk] == d[cname + '_' + f][r][:kk]).all(), (f, r)
+            else:
+                assert np.allclose(ch[f][:kk], d[cname + '_' + f][r][:kk], atol=1e-5), (f, r)
+        info = eng.tree_info(r)
+        assert info['n'] == d[cname + '_root_n'][r] and info['max_depth'] == d[cname + '_maxdepth'][r]
+    assert (eng.root_counts().cpu().numpy() == d[cname + '_counts']).all()
+    assert (eng.root_probs(1.0).cpu().numpy() == d[cname + '_probs'][:, 0]).all()
+    assert (eng.root_probs(0.0).cpu().numpy() == d[cname + '_probs'][:, 4]).all()
+    assert (eng.root_value(False).cpu().numpy() == d[cname + '_vmax']).all()
+    assert (eng.root_value(True).cpu().numpy() == d[cname + '_vavg']).all()
+    assert (eng.tape_counters() == d[cname + '_ctr']).all()
+    eng.counters()
+    eng.close()
+
+
+AGENT = {'plain': (dict(), dict()),
+         'temp': (dict(add_root_temp=True, cpuct=4.0, fpu_reduction=0.4), dict()),
+         'fastmix': (dict(symmetric_samples=False), dict(prob_fast=0.5, fast_sims=3))}
+
+
+@pytest.mark.parametrize('launch', P.LAUNCHES)
+@pytest.mark.parametrize('cname', list(AGENT))
+def test_gb_agent_vs_reference_goldens(cname, launch):
+    d = dict(np.load(os.path.join(G, 'gb_agent.npz')))
+    B, sims, games = int(d[cname + '_B']), int(d[cname + '_sims']), int(d[cname + '_games'])
+    seed, slot_base = int(d[cname + '_seed']), int(d[cname + '_slot_base'])
+    kw, rnd = AGENT[cname]
+    eng = P.engine(game=GB, B=B, seed=seed, slot_base=slot_base, games_per_iteration=games, example_capacity=8192, sims_hint=sims, **kw)
+    rec = P.run_engine_agent(torch, eng, seed, slot_base, sims, games, launch=launch, **rnd)
+    assert (np.array(rec['sims']) == d[cname + '_round_sims']).all()
+    assert (np.array(rec['counts']) == d[cname + '_counts']).all()
+    assert (np.array(rec['actions']) == d[cname + '_actions']).all()
+    assert (np.array(rec['games_played']) == d[cname + '_games_played']).all()
+    assert (np.array(rec['obs_crc'], np.uint32) == d[cname + '_obs_crc']).all()
+    obs, pi, z = [t.cpu().numpy() for t in eng.examples()]
+    assert obs.shape == d[cname + '_s_obs'].shape
+    assert (obs == d[cname + '_s_obs']).all() and (pi == d[cname + '_s_pi']).all() and (z == d[cname + '_s_z']).all()
+    ws, turns, _ = eng.results()
+    assert (ws == d[cname + '_r_ws']).all() and (turns == d[cname + '_r_turns']).all()
+    eng.close()
+
+
+def test_gb_mcts_class_api_vs_reference_goldens():
+    """alphazero_general_amd.MCTS on an envs.gobang.Game object (one slot: the tape stream of gb_tree's root 0), find_leaf /
+    process_results fed the fixture's evaluations, must build the reference's tree: depths, counts, values, probabilities"""
+    from alphazero_general_amd.MCTS import MCTS
+    from alphazero_general_amd.utils import dotdict
+    d = dict(np.load(os.path.join(G, 'gb_tree.npz')))
+    cpuct, fpu, _, _, sims = d['default_cfg']
+    seed, sims = int(d['default_seed']), int(sims)
+    g = _game().from_azg_state(*_states(d['prefix'][:1])[0])
+    m = MCTS(dotdict(cpuct=float(cpuct), fpu_reduction=float(fpu), root_noise_frac=0.1, root_policy_temp=1.1, min_discount=1,
+                     _num_players=3, numMCTSSims=sims, _azg_seed=seed))
+    for s in range(sims):
+        leaf = m.find_leaf(g)
+        assert m.depth == d['default_depth'][0, s]
+        p, v = ol.fake_eval(seed, 0, s, A, NV)
+        m.process_results(leaf, v, p, False, False)
+    assert (np.asarray(m.counts(g)) == d['default_counts'][0]).all()
+    assert m.value(False) == d['default_vmax'][0] and m.value(True) == d['default_vavg'][0]
+    assert (np.asarray(m.probs(g, 1.0), np.float32) == d['default_probs'][0, 0]).all()
+
+
+# ------------------------------------------------------------------------------------------------------------------------- network
+def _reference(key, salt=0, depth=None):
+    argname, over = NETS[key]
+    over = dict(over)
+    if depth is not None:
+        over['depth'] = depth
+    args = R.net_args(argname, **over)
+    x = torch.from_numpy(R.boards('gobang'))
+    sd, ref = R.make_state('gobang', args, 'trained', salt, probe=x)
+    return args, sd, ref, x, ref.forward(x)
+
+
+def _wrapper(args, sd, backend='hip'):
+    from alphazero_general_amd.nnet import NNetWrapper
+    net = NNetWrapper(_game(), args, device=DEV, backend=backend)
+    net.adopt(sd)
+    net.refresh()
+    assert net._hip is not None and net._hip.fact_head
+    return net
+
+
+def _check(name, args, sd, o, x, sizes):
+    net = _wrapper(args, sd)
+    hip = net._hip
+    N = x.shape[0]
+    xg = x.to(DEV)
+    for B in sizes:
+        idx = F._idx(N, B)
+        xb = xg[idx.to(DEV)].contiguous()
+        x8 = hip.to_nhwc8(xb)
+        tag = '%s_B%d' % (name, B)
+        F._stream_cmp(tag, hip, F.tower_stream(hip, x8), o, idx, 1)          # one board per tile at every batch size
+        feat = hip.forward_features_nhwc8(x8).float().cpu().reshape(B, 2, hip.feat_k)
+        assert hip.feat_k == 3616 and hip.A == A and hip.NV == NV
+        f = feat[:, :, :hip.HW * 16].reshape(B, 2, hip.HW, 16)
+        got = torch.cat([f[:, 1], f[:, 0]], 2).permute(0, 2, 1).reshape(B, 32, *o['feat'].shape[2:])
+        sel = F._sel(B)
+        rep = R.stream_report(got[sel], o['feat'][idx[sel]], tile=1)
+        F.record(dict(case=tag, what='head_features', **rep, tau=R.TAU_STREAM))
+        assert rep['ratio'] <= 1.0, (tag, rep)
+        lg = hip.forward_logits_nhwc8(x8).float().cpu()
+        F._logits_cmp(tag + '_fact', lg[:, :hip.A], lg[:, hip.A:hip.A + hip.NV], o, idx)
+        p, v = net.process(xb)
+        F._probs_cmp(tag + '_process', p.cpu(), v.cpu(), o, idx)
+
+
+@pytest.mark.parametrize('key', list(NETS))
+def test_gb_network_vs_fp64(key):
+    args, sd, ref, x, o = _reference(key)
+    _check(key, args, sd, o, x, [1, 37, 301, 2 * F._cus() + 1])
+
+
+@pytest.mark.parametrize('depth', [0, 1, 2, 6])
+@pytest.mark.parametrize('key', ['gobang_32x4', 'gobang_64x4'])
+def test_gb_network_depths_vs_fp64(key, depth):
+    args, sd, ref, x, o = _reference(key, depth=depth)
+    _check('%s_depth%d' % (key, depth), args, sd, o, x, [37, 301])
+
+
+# ------------------------------------------------------------------------------------------------------------------------- search
+def _net(key, salt=7):
+    args, sd, ref, x, o = _reference(key, salt=salt)
+    return _wrapper(args, sd)
+
+
+@pytest.mark.parametrize('key', ['gobang_32x4', 'gobang_64x4'])
+def test_gb_phase_search_on_the_hip_tower(key):
+    """NNetWrapper.process (the HIP tower) drives select / backup / advance for a few moves; the engine's leaf observations are the
+    host env's, and every move played is legal and lands where the host env puts it.  The sparse heads refuse gobang cleanly."""
+    from alphazero_general_amd.engine import DeviceEngine
+    net = _net(key)
+    assert net._hip.can_search
+    Game = _game()
+    B, sims, moves = 256, 24, 3
+    eng = DeviceEngine(GB, B, cpuct=2.0, fpu_reduction=0.1, add_root_temp=True, seed=41, games_per_iteration=1 << 30,
+                       example_capacity=B * (moves + 1) * 8, sims_hint=sims)
+    oc = eng.new_obs(torch.float32)
+    for mv in range(moves):
+        before = [Game.from_azg_state(*s) for s in eng.get_states()]
+        for s in range(sims):
+            eng.select(oc)
+            if s == 0:
+                for i, lf in enumerate(eng.get_leaf_states()[:16]):
+                    assert (oc[i].cpu().numpy() == Game.from_azg_state(*lf).observation()).all()
+            p, v = net.process(oc)
+            eng.backup(p.contiguous(), v.contiguous())
+        eng.advance(True)
+        acts = eng.last_actions().cpu().numpy()
+        after = eng.get_states()
+        for i in range(B):
+            g = before[i]
+            assert g.valid_moves()[acts[i]] == 1
+            g.play_action(int(acts[i]))
+            assert (after[i][0] == g._board.pieces.reshape(-1)).all() and after[i][1] == g.player and after[i][2] == g.turns
+    obs, pi, z = eng.examples()
+    assert obs.shape[1:] == (4, 15, 15) and pi.shape[1] == A and obs.shape[0] == 0 == eng.counters()['games_played']   # (samples: at game end)
+    hip = net._hip
+    feat = hip.forward_features_nhwc8(hip.to_nhwc8(oc))
+    with pytest.raises(Exception) as ei:
+        eng.backup_select_features(feat, hip.head_rows, hip.head2_b, oc, select=True)
+    assert 'UNSUPPORTED' in str(ei.value) or 'sparse' in str(ei.value)
+    with pytest.raises(Exception) as ei:
+        hip.search(eng, sims, exact=False)                   # the sparse persistent launch
+    assert 'UNSUPPORTED' in str(ei.value) or 'sparse' in str(ei.value)
+    eng.close()
+
+
+@pytest.mark.parametrize('key,B,sims,moves', [('gobang_32x4', 768, 60, 3), ('gobang_64x4', 768, 60, 3), ('gobang_64x4', 40, 30, 4)])
+def test_gb_wide_exact_search_vs_phase_loop(key, B, sims, moves):
+    """azg_search_wide_exact_f16 (one game per workgroup; 227-level paths through the game-sized walk mailbox) against select ->
+    NNetWrapper.process -> backup on a twin engine with the same seeds: counts, probabilities, values, moves, samples, results"""
+    from alphazero_general_amd.engine import DeviceEngine
+    net = _net(key)
+    kw = dict(cpuct=4.0, fpu_reduction=0.4, add_root_noise=True, add_root_temp=True, seed=41, games_per_iteration=1 << 30,
+              example_capacity=B * (moves + 1) * 8, sims_hint=sims)
+    ea, ec = DeviceEngine(GB, B, **kw), DeviceEngine(GB, B, **kw)
+    oc = ec.new_obs(torch.float32)
+    for mv in range(moves):
+        net._hip.search(ea, sims, exact=True)
+        for _ in range(sims):
+            ec.select(oc)
+            p, v = net.process(oc)
+            ec.backup(p.contiguous(), v.contiguous())
+        assert torch.equal(ea.root_counts(), ec.root_counts()), mv
+        assert torch.equal(ea.root_probs(1.0), ec.root_probs(1.0)) and torch.equal(ea.root_value(True), ec.root_value(True)), mv
+        ea.advance(True); ec.advance(True)
+        assert torch.equal(ea.last_actions(), ec.last_actions()), mv
+    assert (ea.tape_counters() == ec.tape_counters()).all()
+    assert ea.counters() == ec.counters()
+    for t, u in zip(ea.examples(), ec.examples()):
+        assert torch.equal(t, u)
+    assert all((a == b).all() for a, b in zip(ea.results(), ec.results()))
+    ea.close(); ec.close()
+
+
+def test_gb_wide_search_deep_path():
+    """positions about 200 plies in: the walks of the persistent launch reach terminal leaves and full boards (wins, draws at turn 225)
+    through the game-sized walk mailbox, still equal to the per-phase loop"""
+    from alphazero_general_amd.engine import DeviceEngine
+    net = _net('gobang_64x4')
+    Game = _game()
+    rng = np.random.RandomState(11)
+    states = []
+    while len(states) < 64:
+        g = Game()
+        for a in rng.permutation(A)[:200]:
+            g2 = g.clone(); g2.play_action(int(a))
+            if g2.win_state().any():
+                continue
+            g = g2
+        if g.turns >= 180:
+            states.append(g.to_azg_state())
+    sims = 120
+    kw = dict(cpuct=4.0, fpu_reduction=0.4, seed=17, games_per_iteration=1 << 30, example_capacity=1 << 14, sims_hint=sims)
+    ea, ec = DeviceEngine(GB, 64, **kw), DeviceEngine(GB, 64, **kw)
+    ea.set_states(states); ec.set_states(states)
+    oc = ec.new_obs(torch.float32)
+    net._hip.search(ea, sims, exact=True)
+    for _ in range(sims):
+        ec.select(oc)
+        p, v = net.process(oc)
+        ec.backup(p.contiguous(), v.contiguous())
+    assert torch.equal(ea.root_counts(), ec.root_counts())
+    depth = max(ea.tree_info(i)['max_depth'] for i in range(64))
+    assert depth >= 3 and depth == max(ec.tree_info(i)['max_depth'] for i in range(64))
+    ea.close(); ec.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------- arena
+def _arena_nets(width, n, seed0=20):
+    from alphazero_general_amd import nnet as N
+    from alphazero_general_amd.utils import dotdict
+    na = dotdict(dict(N.DEFAULT_NET_ARGS, num_channels=width))
+    out = []
+    for m in range(n):
+        torch.manual_seed(seed0 + m)
+        w = N.NNetWrapper(_game(), na, device=DEV, dtype=torch.float16)
+        w.refresh()
+        out.append(w)
+    return out
+
+
+def _arena_replay(runs, B):
+    """every slot's games replayed on envs.gobang from the actions of every round: each move legal, each finished game's win state and
+    length the engine's result record"""
+    Game = _game()
+    acts, _, (ws, turns, slot), _ = runs
+    games = [Game() for _ in range(B)]
+    done = [[] for _ in range(B)]
+    for row in acts:
+        for i, a in enumerate(row):
+            if a < 0:
+                continue
+            g = games[i]
+            assert g.valid_moves()[a] == 1, (i, a)
+            g.play_action(int(a))
+            w = g.win_state()
+            if w.any():
+                done[i].append((tuple(int(x) for x in w), g.turns))
+                games[i] = Game()
+    for i in range(B):
+        rec = [(tuple(int(x) for x in ws[j]), int(turns[j])) for j in range(len(slot)) if slot[j] == i]
+        assert rec == done[i][:len(rec)] and len(rec) >= len(done[i]) - 1, i
+    assert sum(len(d) for d in done) > 0
+
+
+@pytest.mark.parametrize('raw', [False, True])
+@pytest.mark.parametrize('width', [32, 64])
+def test_gb_persistent_arena_equals_host_split(width, raw):
+    """two differently seeded nets, or a net against a raw seat (RawMCTSPlayer: policy float32(1 / 225), value zeros): the persistent
+    arena launch, captured and eager, plays exactly the games of the host-split path, and the games replay on the host env"""
+    import test_gpu_arena_wide as W
+    nets = _arena_nets(width, 1 if raw else 2)
+    seats = nets + [None] if raw else nets
+    B = 24
+    runs = W._forms(_game(), seats, W._args(), B, 7 if raw else 5, 'slot' if raw else 'agent', 150)
+    W._same(runs)
+    _arena_replay(runs[0], B)
+
+
+def test_gb_default_routing_takes_the_faster_form():
+    """fused_search=None: gobang's persistent launch measured slower than the per-phase loop (profiles/gobang_throughput.json), so the
+    self-play and arena runners take the per-phase form by default and the persistent one only when asked"""
+    from alphazero_general_amd.selfplay import ArenaRunner, SelfPlayRunner
+    import test_gpu_arena_wide as W
+    nets = _arena_nets(32, 2)
+    assert nets[0]._hip.can_search and not nets[0]._hip.search_preferred
+    args = W._args()
+    r = SelfPlayRunner(_game(), nets[0], args, num_slots=8, seed=3)
+    assert not r.fused_search
+    r.engine.close()
+    r = SelfPlayRunner(_game(), nets[0], args, num_slots=8, seed=3, fused_search=True)
+    assert r.fused_search
+    r.engine.close()
+    a = ArenaRunner(_game(), nets, args, num_slots=8, seed=3, use_graph=False)
+    assert not a.wide_search
+    a.engine.close()
