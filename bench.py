@@ -1,6 +1,6 @@
 """bench.py -- self-play throughput of the MI355X engine on BASELINE.json's configurations.
 
-    python bench.py [--workload connect4|brandubh|arena|trimok] --gpus N --steps K --warmup W [--dump-outputs DIR] [--other-workloads]
+    python bench.py [--workload connect4|brandubh|arena|trimok] --gpus N --steps K --warmup W [--dump-outputs DIR] [--full [--other-workloads]]
 
 Default workload = the headline config (BASELINE.json configs[1]): connect4, 2048 concurrent games per GPU x 100 MCTS sims per
 move, fp16 ResNet 128ch x 8 (envs/connect4/train.py net + search hyper-parameters), random-init weights, games from the empty
@@ -12,15 +12,18 @@ resident in HBM; the only host traffic in the timed region is one counter read p
 N > 1: `python bench.py --gpus N` starts its own N ranks (torch.distributed.run, one per GPU, RCCL); under an external
 torch.distributed.run it uses the ranks it was given.  n_gpus in the output is the number of ranks that actually ran.
 
-Measured inside the run (HIP events on the launch stream, rounds launched eagerly AFTER the timed region, which holds product rounds only):
-`roofline` = the dominant kernel of a simulation step, `tree_roofline` = the tree launch.  `traffic` (HBM bytes per launch) comes
-from the committed rocprofv3 --pmc summary profiles/r03_pmc.json (tools/collect_profiles.py, run on the GPU box), never from a
-constant in this file.  `cpu_baseline` (rank 0, N = 1 only) = the C oracle on the host cores, bounded sample.
+A plain run does only what the headline needs: set-up, --warmup rounds, the --steps timed rounds, --dump-outputs if given, the line.
+`--full` adds what takes work of its own after the timed region, which holds product rounds only:
+  `roofline` = the dominant kernel of a simulation step, `tree_roofline` = the tree launch, from HIP events on the launch stream
+  of rounds launched eagerly after the timed region; `traffic` (HBM bytes per launch) comes from the committed rocprofv3 --pmc summary
+  profiles/r06_pmc.json (tools/collect_profiles.py), never from a constant in this file; `phase_budget` from the committed phase stamps;
+  `sparse_heads` (wide-head workloads: a second run on the opt-in sparse-heads launch); `library_gemm_tflops` (N = 1: hipBLASLt context);
+  `cpu_baseline` (rank 0, N = 1 only) = the C oracle on the host cores, bounded sample.
 
 The result is ONE JSON line, the last line on stdout.  `ms_per_step` = the timed region's wall time over --steps (exactly --steps
-rounds run in it).  `--other-workloads` adds configs 3-5, their shard sizes and compat mode to the connect4 line (a much longer run
-and line).  `--dump-outputs DIR` writes what the timed path handed its caller after the last timed step as DIR/<name>.npy
-(dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared array for array.
+rounds run in it).  `--other-workloads` (implies --full) adds configs 3-5, their shard sizes and compat mode to the connect4 line (a
+much longer run and line).  `--dump-outputs DIR` writes what the timed path handed its caller after the last timed step as
+DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -727,25 +730,29 @@ def main():
     ap.add_argument('--workload', default='connect4', choices=sorted(WORKLOADS))
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--pipelines', type=int, default=1)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-library-gemm', action='store_true', help='skip the hipBLASLt context GEMM (keeps profiler traces to our own kernels)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also measure what the headline does not need: rooflines from eager profile rounds, the '
+                         'sparse-heads run, the hipBLASLt context GEMM, the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-library-gemm', action='store_true', help='with --full: skip the hipBLASLt context GEMM (keeps profiler traces to our own kernels)')
     ap.add_argument('--no-fused-search', action='store_true',
                     help='2 launches per simulation (tower, backup+select) instead of one persistent launch per move (azg_search_f16)')
     ap.add_argument('--other-workloads', action='store_true',
-                    help='connect4, 1 GPU: also time BASELINE configs 3-5, their shard sizes and compat mode (other_workloads, strong_scaling_shards)')
+                    help='connect4, 1 GPU, implies --full: also time BASELINE configs 3-5, their shard sizes and compat mode (other_workloads, strong_scaling_shards)')
     ap.add_argument('--no-other-workloads', action='store_true', help='(the default; kept for older command lines)')
-    ap.add_argument('--profile-rounds', type=int, default=10, help='eager rounds of the persistent launch timed after the timed region')
-    ap.add_argument('--compat', action='store_true', help='also time compat mode (unmodified-Coach protocol: SelfPlayAgent processes served by the parent)')
+    ap.add_argument('--profile-rounds', type=int, default=10, help='with --full: eager rounds of the persistent launch timed after the timed region')
+    ap.add_argument('--compat', action='store_true', help='implies --full: also time compat mode (unmodified-Coach protocol: SelfPlayAgent processes served by the parent)')
     ap.add_argument('--search-heads', default=None, choices=['exact', 'sparse'],
                     help='wide-head workloads, persistent launch: all A + P+1 logits inside the launch (bit-exact) or the valid actions only')
     ap.add_argument('--no-exact-heads', '--no-sparse-heads', dest='no_sparse_heads', action='store_true',
-                    help='skip the second run of the wide-head workloads with the opt-in sparse heads')
+                    help='with --full: skip the second run of the wide-head workloads with the opt-in sparse heads')
     ap.add_argument('--no-shards', action='store_true', help='with --other-workloads: skip the 1 / 2 / 4-GPU shard sizes of configs 3-5')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the timed path returned after its last step as DIR/<name>.npy (float32 / float64, <= 64 MB)')
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error('--steps must be >= 1 and --warmup >= 0')
+    a.full = a.full or a.other_workloads or a.compat
 
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return self_launch(a.gpus)                                    # one rank per GPU under torch.distributed.run
@@ -758,15 +765,16 @@ def main():
     dev = torch.device('cuda', local_rank)
     rank_devices = D.describe_ranks(local_rank)                       # (raises if two ranks share a GPU; the records go on the line)
 
+    # (the example store is sized for --full's profile rounds too, so that the timed path is set up alike with and without it)
     c = build(a.workload, a, rank, local_rank, dev, a.steps + a.warmup + a.profile_rounds + 8)
     t = timed_region(c, a.steps, a.warmup, world, rank)
     dumped = dump_outputs(c, t, a.dump_outputs) if a.dump_outputs and rank == 0 else None   # (before anything else runs on the engines)
     t.pop('exchange')
-    netprof, prof = profile_rounds(c, a.profile_rounds)              # after the timed region
-    ex = None if a.no_sparse_heads else sparse_heads_run(c, a, rank, local_rank, dev, world)   # (every rank: it has its own exchange step)
+    if a.full:
+        netprof, prof = profile_rounds(c, a.profile_rounds)          # after the timed region
+        ex = None if a.no_sparse_heads else sparse_heads_run(c, a, rank, local_rank, dev, world)   # (every rank: it has its own exchange step)
     if rank != 0:
         return 0
-    roofline, roof_tree, roof_net = rooflines(c, netprof, prof)
     dt = t['dt']
     out = {
         'metric': 'mcts_node_expansions_per_sec', 'value': round(t['expansions'] / dt, 1), 'unit': 'expansions/s',
@@ -787,21 +795,23 @@ def main():
         # (example all-gather + tallies, once per timed region)
         'rank_ms_per_step': {'max': round(t['rank_ms_per_step_max'], 3), 'min': round(t['rank_ms_per_step_min'], 3)},
         'exchange_ms': round(t['exchange_ms'], 3),
-        'roofline': roofline, 'tree_roofline': roof_tree,
     }
-    if roof_net is not None and roofline is not roof_net:
-        out['net_roofline'] = roof_net
-    pbud = phase_budget(c, roofline)
-    if pbud is not None:
-        roofline['phase_budget'] = pbud
-    if ex is not None:
-        out['sparse_heads'] = ex
-    if world == 1 and roofline is not None and roofline['bound'] == 'mfma' and not a.no_library_gemm:
-        lib_tf = library_gemm_tflops(dev)                            # outside the timed region
-        roofline['library_gemm_tflops'] = round(lib_tf, 1)
-        roofline['vs_library_gemm'] = round(roofline['achieved'] / lib_tf, 3)
-    if world == 1 and not a.no_cpu_baseline:
-        out['cpu_baseline'] = cpu_baseline(c.W, c.nets, c.arena)
+    if a.full:
+        roofline, roof_tree, roof_net = rooflines(c, netprof, prof)
+        out['roofline'], out['tree_roofline'] = roofline, roof_tree
+        if roof_net is not None and roofline is not roof_net:
+            out['net_roofline'] = roof_net
+        pbud = phase_budget(c, roofline)
+        if pbud is not None:
+            roofline['phase_budget'] = pbud
+        if ex is not None:
+            out['sparse_heads'] = ex
+        if world == 1 and roofline is not None and roofline['bound'] == 'mfma' and not a.no_library_gemm:
+            lib_tf = library_gemm_tflops(dev)                        # outside the timed region
+            roofline['library_gemm_tflops'] = round(lib_tf, 1)
+            roofline['vs_library_gemm'] = round(roofline['achieved'] / lib_tf, 3)
+        if world == 1 and not a.no_cpu_baseline:
+            out['cpu_baseline'] = cpu_baseline(c.W, c.nets, c.arena)
     if dumped is not None:
         out['dumped_outputs'] = dumped
     if world == 1 and a.workload == 'connect4' and a.other_workloads and not a.slots:

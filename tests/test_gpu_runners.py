@@ -171,8 +171,8 @@ def test_bench_two_ranks_on_one_gpu(launcher):
 @pytest.mark.parametrize('workload,slots', [('brandubh', 64), ('arena', 64), ('trimok', 64)])
 def test_bench_two_ranks_other_workloads(workload, slots):
     """the N-rank path of the OTHER bench workloads (BASELINE configs 3-5) before their first contact with a multi-GPU node: two
-    ranks on GPU 0 over gloo, self-launched; brandubh / trimok (timed on the exact persistent launch) also run their opt-in sparse-heads
-    leg on both ranks (its own exchange step), the arena has no example exchange at all."""
+    ranks on GPU 0 over gloo, self-launched, --full; brandubh / trimok (timed on the exact persistent launch) also run their opt-in
+    sparse-heads leg on both ranks (its own exchange step), the arena has no example exchange at all."""
     import json
     import os
     import signal
@@ -182,7 +182,7 @@ def test_bench_two_ranks_other_workloads(workload, slots):
     env = dict(os.environ, AZG_DIST_BACKEND='gloo', AZG_SINGLE_DEVICE='1')
     env.pop('WORLD_SIZE', None); env.pop('RANK', None)
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--workload', workload, '--steps', '5', '--warmup', '1', '--slots', str(slots),
-           '--profile-rounds', '1']
+           '--full', '--profile-rounds', '1']
     p = subprocess.Popen(cmd, cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, start_new_session=True)
     try:
         out, _ = p.communicate(timeout=300)
@@ -210,6 +210,33 @@ def test_bench_refuses_a_rank_count_that_differs_from_gpus():
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '0', '--slots', '64'],
                        cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=240)
     assert r.returncode != 0 and b'"metric"' not in r.stdout and b'rank(s) were launched' in r.stdout
+
+
+def test_bench_plain_run_is_the_headline_and_full_adds_after_it(tmp_path):
+    """one GPU: a plain run prints the headline line without the --full figures (profile rounds, rooflines, CPU baseline); a --full
+    run with the same arguments adds them after the timed region, and both timed paths hand back the same arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = {}
+    for mode in ('plain', 'full'):
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--slots', '64',
+               '--dump-outputs', str(tmp_path / mode)] + (['--full', '--profile-rounds', '1', '--no-library-gemm', '--no-cpu-baseline'] if mode == 'full' else [])
+        r = subprocess.run(cmd, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=240)
+        out = [l for l in r.stdout.decode(errors='replace').splitlines() if l.startswith('{"metric"')]
+        assert r.returncode == 0 and len(out) == 1, r.stdout.decode(errors='replace')[-2000:]
+        lines[mode] = json.loads(out[0])
+    plain, full = lines['plain'], lines['full']
+    for d in (plain, full):
+        assert d['metric'] == 'mcts_node_expansions_per_sec' and d['unit'] == 'expansions/s' and d['higher_is_better'] is True
+        assert d['value'] > 0 and d['ms_per_step'] > 0 and d['steps'] == 3 and d['warmup'] == 1 and d['dtype'] == 'f32 tree / f16 net'
+    assert not {'roofline', 'tree_roofline', 'cpu_baseline', 'sparse_heads'} & set(plain)
+    assert full['roofline'] is not None and 'launch_us_min_median_max' in full['roofline']
+    assert plain['dumped_outputs'] == full['dumped_outputs']
+    for name in plain['dumped_outputs']:
+        assert np.array_equal(np.load(tmp_path / 'plain' / (name + '.npy')), np.load(tmp_path / 'full' / (name + '.npy'))), name
 
 
 @pytest.mark.parametrize('game', ['brandubh', 'trimok'])

@@ -93,7 +93,7 @@ def main():
     for w in a.workloads:
         # (name or name@slots: a shard size of the workload, e.g. brandubh@2048 -- config 3's 2-GPU shard, four games per workgroup)
         wname, _, wslots = w.partition('@')
-        base = ['--workload', wname, '--no-cpu-baseline', '--no-library-gemm', '--no-other-workloads', '--no-sparse-heads'] + (['--slots', wslots] if wslots else [])
+        base = ['--workload', wname, '--full', '--no-cpu-baseline', '--no-library-gemm', '--no-other-workloads', '--no-sparse-heads'] + (['--slots', wslots] if wslots else [])
         w = w.replace('@', '_')
         out, line, rc = rocprof('kt_' + w, ['--kernel-trace', '--stats'], base + ['--steps', '12', '--warmup', '2'])
         stats = glob.glob(os.path.join(out, '**', '*kernel_stats.csv'), recursive=True)

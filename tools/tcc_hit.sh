@@ -1,6 +1,7 @@
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for cfg in "brandubh 2048" "brandubh 512"; do set -- $cfg
-rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum --output-format csv -d /tmp/tcc_$2 -- python $GRAFT_REPO_ROOT/bench.py --workload $1 --slots $2 --steps 3 --warmup 1 --no-cpu-baseline --no-library-gemm --no-other-workloads --no-sparse-heads --profile-rounds 1 > /dev/null 2>&1
+rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum --output-format csv -d /tmp/tcc_$2 -- python $R/bench.py --workload $1 --slots $2 --steps 3 --warmup 1 --full --no-cpu-baseline --no-library-gemm --no-other-workloads --no-sparse-heads --profile-rounds 1 > /dev/null 2>&1
 python - $2 <<'PY'
 import csv,glob,sys
 acc={}
