@@ -501,11 +501,13 @@ template <class G, int HW, bool COMPACT = false> struct WideScratch {
 // + biases (the same for every game and simulation: fetched once per launch instead of once per simulation by every walker;
 // COMPACT: they stay in global memory)
 template <class G> struct WideMailFits { static_assert(G::MAX_TURNS + 2 <= (int)(sizeof(WalkMailOf<G>::act) / sizeof(int)), "WalkMail::act holds one action per level of a find_leaf path"); };
-template <class G, int HW, int BOARDS, bool COMPACT = false> struct WideLds : WideMailFits<G> {
+// (NOVAL: the exact-only tiles of the streamed heads, heads_full_stream -- no sparse value rows are ever read there, and at 15x15 x 128
+//  channels their 21 KB are what an 8-block tower's parameters need)
+template <class G, int HW, int BOARDS, bool COMPACT = false, bool NOVAL = false> struct WideLds : WideMailFits<G> {
     static constexpr int NV = G::P + 1, FK = WideScratch<G, HW, COMPACT>::FK;
     // (ZERO: a feature row of zeros -- the A-operand rows of heads_full_lds that no board stands behind; zeroed once per launch)
-    static constexpr int ERR = BOARDS * WideScratch<G, HW, COMPACT>::BYTES, ZERO = (ERR + 16 + 15) / 16 * 16, VROWS = ZERO + FK * 2, VBIAS = VROWS + (COMPACT ? 0 : NV * FK * 2),
-                         BYTES = (VBIAS + (COMPACT ? 0 : NV * 4) + 15) / 16 * 16;
+    static constexpr int ERR = BOARDS * WideScratch<G, HW, COMPACT>::BYTES, ZERO = (ERR + 16 + 15) / 16 * 16, VROWS = ZERO + FK * 2, VBIAS = VROWS + (COMPACT || NOVAL ? 0 : NV * FK * 2),
+                         BYTES = (VBIAS + (COMPACT || NOVAL ? 0 : NV * 4) + 15) / 16 * 16;
 };
 
 // The full-width heads of a tile's boards inside the persistent launch (EXACT): logits[board][o] for all A policy outputs and the
@@ -535,7 +537,7 @@ template <int KS, int KQ> struct HeadsOrder {
 #ifndef HEADS_A_RING
 #define HEADS_A_RING 4
 #endif
-template <class G, int HW> struct HeadsFirst { half8 b[WideScratch<G, HW>::FK / 32]; float bias; };
+template <class G, int HW, int NB = WideScratch<G, HW>::FK / 32> struct HeadsFirst { half8 b[NB]; float bias; };
 // VFIRST (the overlapped one-game tile): the wavefronts take ITEMS instead of subtiles -- item 0 is the value subtile, item j > 0
 // the policy subtile j - 1 -- so that the first thing streaming wavefront 0 finishes is the value row the walker is waiting for
 template <int OSP, bool VFIRST> __device__ __forceinline__ int heads_item_subtile(int j) { return VFIRST ? (j == 0 ? OSP : min(j - 1, OSP)) : min(j, OSP); }
@@ -634,6 +636,119 @@ __device__ __forceinline__ void heads_full_lds(char *scr0, const char *zero_row,
     }
 }
 
+// STREAMED exact heads (long feat_k: gobang's 15x15 board has FK = 3616, 113 k-steps).  heads_full_lds keeps a whole subtile's KS weight
+// fragments in registers and unrolls both of its loops; at KS = 113 that is 452 registers of fragments, i.e. scratch.  Here the fragments
+// go through a ring of HEADS_STREAM_RING registers that runs that many k-steps ahead of the MFMAs, across subtile boundaries, and the
+// A operand through a ring of the same depth.  The consumption order is HeadsOrder's (position p = 4 j + q is k-step q * KQ + j while all
+// four quarters have a row j; the last quarter is the short one): the rows whose read-ahead stays inside those are a ROLLED loop of two
+// rows = one turn of the ring per iteration (the ring slots are compile-time, the addresses advance by two k-steps), the rest of the
+// subtile is unrolled and requests the next subtile's first turn, position p' into slot p' (so the subtile loop sees the same ring phase
+// in every iteration).  The arithmetic is heads_full_lds's and k_heads_fact's: four chains, one per contiguous quarter, each in ascending
+// k-step order, (q0 + q1) + (q2 + q3) + bias -- the same bits.  A wavefront whose next item lies past the value subtile stops instead of
+// repeating it: with 12 wavefronts and 16 subtiles that is a third of the stream.
+// (the 32- and 64-channel gobang launches keep heads_full_lds until they have an A/B of their own)
+constexpr int HEADS_STREAM_RING = 8;
+template <class G, int HW, int C> constexpr bool heads_streamed() { return WideScratch<G, HW>::FK / 32 > 64 && C >= 128; }
+// (of a kernel's SEARCH argument: false for everything but the exact wide modes; a trait, not a lambda in the kernel -- the kernel's
+//  lambdas are numbered in its symbols, and one more changes a pre-existing instantiation's code)
+template <class SEARCH, int HW, int C, class = void> struct HeadsStreamedOf { static constexpr bool value = false; };
+template <class SEARCH, int HW, int C> struct HeadsStreamedOf<SEARCH, HW, C, std::enable_if_t<SEARCH::WIDE && SEARCH::EXACT>> {
+    static constexpr bool value = heads_streamed<typename SEARCH::Game, HW, C>();
+};
+template <class G, int HW, int NW>
+__device__ __forceinline__ void heads_stream_prefetch(const HeadsFull &hf, int wave, int lane, HeadsFirst<G, HW, HEADS_STREAM_RING> &pf) {
+    constexpr int A = G::A, NV = G::P + 1, KS = WideScratch<G, HW>::FK / 32, KQ = (KS + HEADF_Q - 1) / HEADF_Q, OSP = (A + 15) / 16, R = HEADS_STREAM_RING;
+    static_assert(NW <= OSP + 1, "every wavefront has a first subtile of its own");
+    constexpr HeadsOrder<KS, KQ> ord;
+    const int i16 = lane & 15, s0 = wave;
+    const half8 *w0 = s0 == OSP ? hf.wv + lane : hf.wps + (size_t)s0 * (KS * 64) + lane;
+    pf.bias = hf.bias[min(s0 == OSP ? A + i16 : s0 * 16 + i16, A + NV - 1)];
+#pragma unroll
+    for (int p = 0; p < R; p++) pf.b[p] = w0[(size_t)ord.ks[p] * 64];
+    __builtin_amdgcn_sched_barrier(0);                      // (as heads_full_prefetch: the requests stay in front of the head convolutions)
+}
+template <class G, int HW, int BOARDS, int NW, bool COMPACT>
+__device__ __forceinline__ void heads_full_stream(char *scr0, const char *zero_row, const HeadsFull &hf, int wave, int lane, HeadsFirst<G, HW, HEADS_STREAM_RING> &pf) {
+    using WS = WideScratch<G, HW, COMPACT>;
+    constexpr int A = G::A, NV = G::P + 1, FK = WS::FK, KS = FK / 32, KQ = (KS + HEADF_Q - 1) / HEADF_Q, OSP = (A + 15) / 16, R = HEADS_STREAM_RING;
+    constexpr int NIT = (OSP + 1 + NW - 1) / NW;                             // subtiles per wavefront at most
+    constexpr int JF = KS - (HEADF_Q - 1) * KQ;                              // rows j in which all four quarters have a k-step
+    constexpr int JR = (JF - 2) / 2 * 2, PT = HEADF_Q * JR;                  // rows of the rolled loop; first position of the unrolled rest
+    static_assert(BOARDS <= 16 && HEADF_Q == 4 && R == 2 * HEADF_Q, "the tile's boards are the D rows; four K quarters; a ring turn is two rows");
+    static_assert(JF >= 6 && KS - PT >= R && NW <= OSP + 1, "a rolled part, and a rest that holds the next subtile's first turn");
+    const int g = lane >> 4, i16 = lane & 15;
+    const bool live = i16 < BOARDS;
+    const char *fb = live ? scr0 + i16 * WS::BYTES + WS::FEAT + g * 16 : zero_row + g * 16;
+    const int vhalf = live ? FK * 2 : 0;
+    auto frags = [&](int s_) { return s_ == OSP ? hf.wv + lane : hf.wps + (size_t)s_ * (KS * 64) + lane; };
+    constexpr HeadsOrder<KS, KQ> ord;
+    half8 (&b)[R] = pf.b;                                                    // (heads_stream_prefetch: positions 0 .. R - 1 of the first subtile)
+    half8 ar[R];
+    float bias_cur = pf.bias, bias_nxt = 0.f;
+    {
+        const char *f0 = fb + (wave == OSP ? vhalf : 0);
+#pragma unroll
+        for (int p = 0; p < R; p++) ar[p] = *reinterpret_cast<const half8 *>(f0 + ord.ks[p] * 64);
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; it++) {
+        int sc = wave + it * NW;                                             // (scalar: the wave number is)
+        asm volatile("" : "+s"(sc));                                         // (opaque, as heads_full_lds: an iteration's addresses are computed in it)
+        if (sc > OSP) break;
+        const int sn = sc + NW;
+        const bool is_v = sc == OSP;
+        const half8 *wc = frags(sc), *wn = frags(min(sn, OSP));
+        const char *f = fb + (is_v ? vhalf : 0), *fn = fb + (sn >= OSP ? vhalf : 0);
+        if (it + 1 < NIT) bias_nxt = hf.bias[min(sn == OSP ? A + i16 : sn * 16 + i16, A + NV - 1)];
+        floatx4 acc[HEADF_Q];
+#pragma unroll
+        for (int q = 0; q < HEADF_Q; q++) acc[q] = (floatx4){0.f, 0.f, 0.f, 0.f};
+        {
+            const half8 *wj = wc + 2 * 64;                                   // slot u = (row j + u / 4, quarter u % 4); its refill is two rows on
+            const char *fj = f + 2 * 64;
+            auto turn = [&]() __attribute__((always_inline)) {
+#pragma unroll
+                for (int u = 0; u < R; u++) {
+                    const int koff = (u % HEADF_Q) * KQ + u / HEADF_Q;
+                    acc[u % HEADF_Q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ar[u], b[u], acc[u % HEADF_Q], 0, 0, 0);
+                    b[u] = wj[(size_t)koff * 64];
+                    ar[u] = *reinterpret_cast<const half8 *>(fj + koff * 64);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);       // (one fragment request and one A read behind every MFMA)
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                }
+                wj += 2 * 64; fj += 2 * 64;
+            };
+            // (the first turn stands in front of the loop: the requests of a subtile's first turn were issued in the order 1 .. R - 1, 0 by
+            //  the previous subtile's rest, and merged into the loop head that order made every iteration wait for all but one request)
+            turn();
+#pragma unroll 1
+            for (int j = 2; j < JR; j += 2) turn();
+        }
+#pragma unroll
+        for (int p = PT; p < KS; p++) {
+            const int q = ord.q[p], slot = p % R;
+            acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ar[slot], b[slot], acc[q], 0, 0, 0);
+            if (p + R < KS) {
+                b[slot] = wc[(size_t)ord.ks[p + R] * 64];
+                ar[slot] = *reinterpret_cast<const half8 *>(f + ord.ks[p + R] * 64);
+            } else if (it + 1 < NIT) {                                       // (the next subtile's position `slot` into slot `slot`; branch-free:
+                b[slot] = wn[(size_t)ord.ks[slot] * 64];                     //  a wavefront without a next subtile re-reads one turn of the value subtile's)
+                ar[slot] = *reinterpret_cast<const half8 *>(fn + ord.ks[slot] * 64);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const floatx4 sum = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+        const int out = is_v ? A + i16 : sc * 16 + i16, lim = is_v ? A + NV : A;
+        if (4 * g < BOARDS && out < lim) {                                   // D[m = board 4 g + r][n = output i16]
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+                if (4 * g + r < BOARDS) *reinterpret_cast<float *>(scr0 + (4 * g + r) * WS::BYTES + WS::LG + out * 4) = sum[r] + bias_cur;
+        }
+        bias_cur = bias_nxt;
+    }
+}
+
 // (the wide search mode keeps one workgroup per CU busy for a whole move and mixes three phases with different register needs:
 //  one wave per SIMD, the whole register file)
 // SOLO tree phase (fewer than two wavefronts per game: several games per workgroup at large batches): wave b does ALL of game b's
@@ -691,6 +806,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
     static_assert(!IS_WIDE || (C / 32) * PSPLIT * KSPLIT >= BOARDS, "wide search mode: at least one wavefront per game");
     constexpr bool SOLO = IS_WIDE && wide_solo<C, PSPLIT, KSPLIT, BOARDS>();
     constexpr bool EXACT = []() { if constexpr (IS_WIDE) return SEARCH::EXACT; else return false; }();
+    constexpr bool HSTREAM = HeadsStreamedOf<SEARCH, H * W, C>::value;
     constexpr int OVL_NW = wide_overlap_nw<SEARCH, BOARDS, C * 2 * PSPLIT * KSPLIT / 64>();
     constexpr bool OVL = OVL_NW > 0;
     static_assert(OVL_NW == 0 || OVL_NW == 2, "overlapped tile: waves 1 and 2 stream, wave 3 follows the walk");
@@ -698,7 +814,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
     constexpr int NT = C * 2 * PSPLIT * KSPLIT, KS = C / 32, CPR = C / 8;   // threads, k-steps per tap, 16-B chunks per row
     constexpr bool KHALF = tower_khalf_order<H, W, C>();
     constexpr int XCHG_OFF = []() {                              // the k-split exchange area: behind the image and the wide search mode's scratch
-        if constexpr (IS_WIDE) return GEO::TILE + WideLds<typename SEARCH::Game, GEO::HW, BOARDS, wide_solo<C, PSPLIT, KSPLIT, BOARDS>()>::BYTES; else return GEO::TILE;
+        if constexpr (IS_WIDE) return GEO::TILE + WideLds<typename SEARCH::Game, GEO::HW, BOARDS, wide_solo<C, PSPLIT, KSPLIT, BOARDS>(), HSTREAM>::BYTES; else return GEO::TILE;
     }();
     static_assert(KSPLIT == 1 || (KSPLIT == 2 && KS == 2 && KHALF), "k-split: 64-channel towers in k-half order");
     constexpr int NSUBT = GEO::NSUB, NSUB = (NSUBT + PSPLIT - 1) / PSPLIT;   // subtiles of the tile / of one wave
@@ -724,7 +840,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
     }
     for (int c = tid; c < TILE / 16; c += NT) reinterpret_cast<uint4 *>(smem)[c] = make_uint4(0, 0, 0, 0);   // pads stay 0
     if constexpr (IS_WIDE) {                                     // (the feature rows' padding must read as zero)
-        using WL = WideLds<typename SEARCH::Game, HW, BOARDS, SOLO>;
+        using WL = WideLds<typename SEARCH::Game, HW, BOARDS, SOLO, HSTREAM>;
         for (int c = tid; c < WL::VROWS / 16; c += NT) reinterpret_cast<uint4 *>(smem + TILE)[c] = make_uint4(0, 0, 0, 0);
         constexpr int A_ = SEARCH::Game::A;
         if constexpr (!SOLO && !EXACT) {
@@ -820,7 +936,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
             P.w = M.w; P.bias = M.bias; P.pre_scale = M.pre_scale; P.pre_shift = M.pre_shift; P.head1_w = M.head1_w; P.head1_b = M.head1_b;
             hfs = M.hf;
             raw = M.w == nullptr;
-            if (tid == 0) reinterpret_cast<int *>(smem + TILE + WideLds<typename SEARCH::Game, GEO::HW, BOARDS, SOLO>::ERR)[1] = wmover | (raw ? 16 : 0);
+            if (tid == 0) reinterpret_cast<int *>(smem + TILE + WideLds<typename SEARCH::Game, GEO::HW, BOARDS, SOLO, HSTREAM>::ERR)[1] = wmover | (raw ? 16 : 0);
         }
         const half8 *wl = reinterpret_cast<const half8 *>(P.w) + (size_t)(2 * cg) * 64 + lane;
         const half8 *wm0 = wl + (size_t)(STEM_KSTEPS + (KSPLIT == 2 ? kg : 0)) * GEO::WSTEP;      // the wave's main stream (see stream_frag)
@@ -868,7 +984,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
             char *ws = smem + TILE + bd * WS::BYTES;
             float *lg = reinterpret_cast<float *>(ws + WS::LG);
             int *flags = reinterpret_cast<int *>(ws + WS::FLAGS);
-            int *errw = reinterpret_cast<int *>(smem + TILE + WideLds<G, HW, BOARDS, SOLO>::ERR);
+            int *errw = reinterpret_cast<int *>(smem + TILE + WideLds<G, HW, BOARDS, SOLO, HSTREAM>::ERR);
             if (sim == 0 && tid < WS::NFLAGS * BOARDS) reinterpret_cast<int *>(smem + TILE + (tid / WS::NFLAGS) * WS::BYTES + WS::FLAGS)[tid % WS::NFLAGS] = 0;
             // (overlapped tile: the wavefronts reach this point at different times -- later checks sit behind the head convolutions' barrier)
             if (OVL ? sim == 0 : (sim & 15) == 0) {                  // sticky device error: stop, uniformly over the workgroup
@@ -976,7 +1092,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
                     float val[NV];
                     float pv = 0.f;
                     if (!hr.leaf_e) {                                // (a terminal leaf backs its win state up, not the network)
-                        using WL = WideLds<G, HW, BOARDS, SOLO>;
+                        using WL = WideLds<G, HW, BOARDS, SOLO, HSTREAM>;
                         HeadRows hv = sa.hd;                         // the value rows and biases out of LDS (offset so that row A + r lands on them)
                         if constexpr (!SOLO) {
                             hv.rows = reinterpret_cast<const _Float16 *>(smem + TILE + WL::VROWS) - (size_t)A * sa.hd.fk;
@@ -1308,17 +1424,19 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
             // compute them for their own pixel subtiles straight out of the image (the final stream)
             [[maybe_unused]] _Float16 *feat_lds = nullptr;       // wide search mode: the features stay in LDS
             if constexpr (IS_WIDE) feat_lds = reinterpret_cast<_Float16 *>(smem + TILE + WideScratch<typename SEARCH::Game, HW, SOLO>::FEAT);
-            [[maybe_unused]] HeadsFirst<typename std::conditional<IS_WIDE, typename WideGameOf<SEARCH>::type, C4>::type, HW> hfirst;
+            using HGame = typename std::conditional<IS_WIDE, typename WideGameOf<SEARCH>::type, C4>::type;
+            [[maybe_unused]] HeadsFirst<HGame, HW, HSTREAM ? HEADS_STREAM_RING : WideScratch<HGame, HW>::FK / 32> hfirst;
             // (one-game tiles only: the 100 registers the fragments wait in cost the multi-game tiles more in spills than the round trip:
             //  brandubh 512 games 7.24 -> 7.03 ms per move, 2048 games 15.19 -> 15.61 with it, same box)
             constexpr bool HEADS_EARLY = EXACT && BOARDS == 1;
             if constexpr (OVL) {                                 // (the streaming wavefronts; items instead of subtiles: value first)
                 if (wave >= 1 && wave <= OVL_NW) heads_full_prefetch<typename SEARCH::Game, HW, OVL_NW, true>(hfs, wave - 1, lane, hfirst);
                 if (IS_WIDE && tid == 0 && (sim & 15) == 15) {   // (the sticky-error look, every 16th simulation: read behind the barrier below)
-                    using WLE = WideLds<typename WideGameOf<SEARCH>::type, HW, BOARDS, SOLO>;
+                    using WLE = WideLds<typename WideGameOf<SEARCH>::type, HW, BOARDS, SOLO, HSTREAM>;
                     *reinterpret_cast<int *>(smem + TILE + WLE::ERR) = sa_error_word(sa);
                 }
             } else
+            if constexpr (HSTREAM) { static_assert(HEADS_EARLY && !OVL, "streamed heads: the one-game exact tile"); heads_stream_prefetch<typename SEARCH::Game, HW, NT / 64>(hfs, wave, lane, hfirst); } else
             if constexpr (HEADS_EARLY) heads_full_prefetch<typename SEARCH::Game, HW, NT / 64>(hfs, wave, lane, hfirst);
             if (cg == 0) {
                 int opaque = 0;
@@ -1374,19 +1492,21 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
                     // no barrier from here to the next tower: wave 0 goes straight on to walk (it waits for the value row by flag), wave 3
                     // to the masks and the rules, waves 1 .. NW stream the head matrix; wave 2 then reports its policy subtiles
                     using WSO = WideScratch<typename SEARCH::Game, HW, SOLO>;
-                    using WLO = WideLds<typename SEARCH::Game, HW, BOARDS, SOLO>;
+                    using WLO = WideLds<typename SEARCH::Game, HW, BOARDS, SOLO, HSTREAM>;
                     if ((sim & 15) == 15 && *reinterpret_cast<const int *>(smem + TILE + WLO::ERR)) break;   // (uniform: every wavefront reads the word behind the barrier)
                     int *flags_ = reinterpret_cast<int *>(smem + TILE + WSO::FLAGS);
                     if (wave >= 1 && wave <= OVL_NW) {
                         heads_full_lds<typename SEARCH::Game, HW, BOARDS, OVL_NW, SOLO, true>(smem + TILE, smem + TILE + WLO::ZERO, hfs, wave - 1, lane, hfirst, &flags_[3], sim + 1);
                         if (wave == 2) flag_set_gen(&flags_[2], sim + 1, lane);
                     }
+                } else if constexpr (HSTREAM) {
+                    heads_full_stream<typename SEARCH::Game, HW, BOARDS, NT / 64, SOLO>(smem + TILE, smem + TILE + WideLds<typename SEARCH::Game, HW, BOARDS, SOLO, HSTREAM>::ZERO, hfs, wave, lane, hfirst);
                 } else if constexpr (HEADS_EARLY) {
-                    heads_full_lds<typename SEARCH::Game, HW, BOARDS, NT / 64, SOLO>(smem + TILE, smem + TILE + WideLds<typename SEARCH::Game, HW, BOARDS, SOLO>::ZERO, hfs, wave, lane, hfirst);
+                    heads_full_lds<typename SEARCH::Game, HW, BOARDS, NT / 64, SOLO>(smem + TILE, smem + TILE + WideLds<typename SEARCH::Game, HW, BOARDS, SOLO, HSTREAM>::ZERO, hfs, wave, lane, hfirst);
                 } else if constexpr (EXACT) {
                     HeadsFirst<typename SEARCH::Game, HW> hl;
                     heads_full_prefetch<typename SEARCH::Game, HW, NT / 64>(hfs, wave, lane, hl);
-                    heads_full_lds<typename SEARCH::Game, HW, BOARDS, NT / 64, SOLO>(smem + TILE, smem + TILE + WideLds<typename SEARCH::Game, HW, BOARDS, SOLO>::ZERO, hfs, wave, lane, hl);
+                    heads_full_lds<typename SEARCH::Game, HW, BOARDS, NT / 64, SOLO>(smem + TILE, smem + TILE + WideLds<typename SEARCH::Game, HW, BOARDS, SOLO, HSTREAM>::ZERO, hfs, wave, lane, hl);
                 }
                 AZG_WPHASE(4);
 #ifdef AZG_TOWER_TIMING
@@ -1503,7 +1623,7 @@ __global__ __launch_bounds__(C * 2 * PSPLIT * KSPLIT, tower_min_blocks<SEARCH>()
             using WS = WideScratch<G, HW, SOLO>;
             __syncthreads();
             const int bd = wave % BOARDS, role = wave / BOARDS, slot = tile * BOARDS + bd;
-            const int tree = IS_WARENA ? slot * sa.ev.T + (reinterpret_cast<const int *>(smem + TILE + WideLds<G, HW, BOARDS, SOLO>::ERR)[1] & 15) : slot;
+            const int tree = IS_WARENA ? slot * sa.ev.T + (reinterpret_cast<const int *>(smem + TILE + WideLds<G, HW, BOARDS, SOLO, HSTREAM>::ERR)[1] & 15) : slot;
             if (lds_live && role == 0 && slot < sa.ev.B) {
                 const char *ws = smem + TILE + bd * WS::BYTES;
                 if (lane < 4) reinterpret_cast<uint4 *>(sa.ev.hdr + tree)[lane] = reinterpret_cast<const uint4 *>(ws + WS::HDR)[lane];

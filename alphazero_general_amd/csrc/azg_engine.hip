@@ -806,7 +806,8 @@ static int launch_tower(hipStream_t s, const TowerParams &P, SEARCH sa = SEARCH{
     constexpr bool IS_SEARCH = !__is_same(SEARCH, NoSearch);
     using GEO = TowerGeom<H, W, BOARDS, C>;
     constexpr size_t LDS_IMG = []() {                          // the image (+ the wide search mode's scratch behind it)
-        if constexpr (IS_SEARCH) { if constexpr (SEARCH::WIDE) return (size_t)GEO::TILE + (size_t)WideLds<typename SEARCH::Game, H * W, BOARDS, wide_solo<C, PSPLIT, KSPLIT, BOARDS>()>::BYTES; }
+        if constexpr (IS_SEARCH) { if constexpr (SEARCH::WIDE) return (size_t)GEO::TILE + (size_t)WideLds<typename SEARCH::Game, H * W, BOARDS, wide_solo<C, PSPLIT, KSPLIT, BOARDS>(),
+                                                                                                             HeadsStreamedOf<SEARCH, H * W, C>::value>::BYTES; }
         return (size_t)GEO::TILE;
     }();
     // (+ the k-split exchange area: per wave one 1 KB accumulator tile for each of the 2 x NSUB / 2 tiles its partner finishes)
@@ -1210,10 +1211,12 @@ static int wide_tile_launch(azg_engine *e, hipStream_t s, const TowerParams &P, 
         if (bt == 2) return launch_tower<OT::H, OT::W, 2, 64, 2, SW>(s, P, sa, init, occ);
         if (bt == 3) return launch_tower<OT::H, OT::W, 3, 64, 2, SW>(s, P, sa, init, occ);
         if (bt == 4) return launch_tower<OT::H, OT::W, 4, 64, 2, SW>(s, P, sa, init, occ);
-    } else if (game == AZG_GAME_GOBANG && (channels == 32 || channels == 64)) {
-        // the one-game tile of the stand-alone 15x15 towers (three pixel groups of five subtiles; walker, helper, mask wave and, at 64
-        // channels, the rules wave); exact heads only -- gobang has no sparse heads
+    } else if (game == AZG_GAME_GOBANG && (channels == 32 || channels == 64 || channels == 128)) {
+        // the one-game tile of the stand-alone 15x15 towers (three pixel groups of five subtiles; walker, helper, mask wave and, from 64
+        // channels, the rules wave); exact heads only -- gobang has no sparse heads.  128 channels (envs/gobang/train.py's 128 x 8 net):
+        // twelve wavefronts, one workgroup per CU, the streamed heads loop (heads_full_stream)
         if constexpr (EXACT) {
+            if (bt == 1 && channels == 128) return launch_tower<GB::H, GB::W, 1, 128, 3, SearchWide<GB, 1, EXACT>>(s, P, SearchWide<GB, 1, EXACT>{e->v, sims, hd, hf}, init, occ);
             if (bt == 1 && channels == 32) return launch_tower<GB::H, GB::W, 1, 32, 3, SearchWide<GB, 1, EXACT>>(s, P, SearchWide<GB, 1, EXACT>{e->v, sims, hd, hf}, init, occ);
             if (bt == 1 && channels == 64) return launch_tower<GB::H, GB::W, 1, 64, 3, SearchWide<GB, 1, EXACT>>(s, P, SearchWide<GB, 1, EXACT>{e->v, sims, hd, hf}, init, occ);
         }
@@ -1223,7 +1226,7 @@ static int wide_tile_launch(azg_engine *e, hipStream_t s, const TowerParams &P, 
 
 static int wide_max_tile(int game, int channels) {
     if ((game == AZG_GAME_BRANDUBH || game == AZG_GAME_OTHELLO) && channels == 64) return 4;
-    if (game == AZG_GAME_GOBANG && (channels == 32 || channels == 64)) return 1;
+    if (game == AZG_GAME_GOBANG && (channels == 32 || channels == 64 || channels == 128)) return 1;
     if ((game == AZG_GAME_TRIMOK && channels == 32) || (game == AZG_GAME_CONNECT4 && (channels == 32 || channels == 64)) || (game == AZG_GAME_OTHELLO && channels == 32)) return 2;
     return 0;
 }
@@ -1374,7 +1377,7 @@ static int search_wide(azg_engine *e, void *stream, const void *w, const float *
     const int A = e->gi.action_size, NV = e->gi.num_players + 1, hw = e->gi.obs_h * e->gi.obs_w;
     if (feat_k != (hw * 16 + 31) / 32 * 32) return fail(AZG_E_INVALID_ARG, "feat_k must be H*W*16 rounded up to 32");
     if (wide_max_tile(e->cfg.game, channels) == 0)
-        return fail(AZG_E_UNSUPPORTED, "persistent wide-head search: brandubh x 64, the 3-player env x 32, connect4 x {32, 64}, othello x {32, 64} and gobang x {32, 64} channels (use azg_select / network / azg_backup)");
+        return fail(AZG_E_UNSUPPORTED, "persistent wide-head search: brandubh x 64, the 3-player env x 32, connect4 x {32, 64}, othello x {32, 64} and gobang x {32, 64, 128} channels (use azg_select / network / azg_backup)");
     if (!EXACT && e->cfg.game == AZG_GAME_GOBANG) return fail(AZG_E_UNSUPPORTED, "no sparse heads for gobang (use the exact persistent launch)");
     TowerParams P{nullptr, w, bias, pre_scale, pre_shift, nullptr, e->v.B, nblocks, nullptr, nullptr, nullptr, nullptr, A, NV, nullptr, head1_w, head1_b, nullptr, feat_k,
                   nullptr, 0, {}};
@@ -1449,7 +1452,7 @@ extern "C" int azg_search_arena_wide_exact_f16(azg_engine *e, void *stream, int 
     const int game = e->cfg.game;
     if (!e->v.arena || wide_max_tile(game, channels) == 0)
         return fail(AZG_E_UNSUPPORTED, "the persistent wide arena launch is built for arena engines on brandubh x 64, the 3-player env x 32, connect4 x {32, 64} "
-                                       "othello x {32, 64} and gobang x {32, 64} channels (use azg_select / network / azg_backup)");
+                                       "othello x {32, 64} and gobang x {32, 64, 128} channels (use azg_select / network / azg_backup)");
     if (nmodels < e->gi.num_players || nmodels > 4) return fail(AZG_E_INVALID_ARG, "one model per player, at most 4");
     const int A = e->gi.action_size, NV = e->gi.num_players + 1, hw = e->gi.obs_h * e->gi.obs_w;
     if (feat_k != (hw * 16 + 31) / 32 * 32) return fail(AZG_E_INVALID_ARG, "feat_k must be H*W*16 rounded up to 32");
@@ -1487,6 +1490,7 @@ extern "C" int azg_search_arena_wide_exact_f16(azg_engine *e, void *stream, int 
     else if (game == AZG_GAME_OTHELLO && channels == 64) r = wide_arena_tile<OT, 64, 1, 2, 2>(s, P, sa0, init);
     else if (game == AZG_GAME_GOBANG && channels == 32) r = wide_arena_tile<GB, 32, 3, 1, 1>(s, P, sa0, init);
     else if (game == AZG_GAME_GOBANG && channels == 64) r = wide_arena_tile<GB, 64, 3, 1, 1>(s, P, sa0, init);
+    else if (game == AZG_GAME_GOBANG && channels == 128) r = wide_arena_tile<GB, 128, 3, 1, 1>(s, P, sa0, init);
     if (r == AZG_E_UNSUPPORTED) { g_kev = nullptr; return fail(r, "persistent wide arena launch: no tile for this game / width"); }
     if (!init) netprof_end(s, 2, prof, ep);
     return r;

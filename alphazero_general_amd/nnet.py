@@ -409,16 +409,19 @@ class HipResNet:
     def can_search(self):
         """a persistent search launch exists for this network: connect4 x 128 channels with fused heads (azg_search_f16), or
         factorised heads on brandubh x 64 / the 3-player env x 32 / connect4 x {32, 64} / othello x {32, 64} channels -- the reference's
-        default net (Coach.py:108-116) is the 32-channel one -- (azg_search_wide_exact_f16 / azg_search_wide_f16); gobang x {32, 64}
-        channels with exact heads only (azg_search_wide_exact_f16; its 128 x 8 net is searched launch per phase)."""
+        default net (Coach.py:108-116) is the 32-channel one -- (azg_search_wide_exact_f16 / azg_search_wide_f16); gobang x {32, 64, 128}
+        channels with exact heads only (azg_search_wide_exact_f16; 128 is the width of its own 128 x 8 training net, GOBANG_NET_ARGS)."""
         return (self.fused_head and self.game == 0 and self.CH == 128) or (self.fact_head and (self.game, self.CH) in ((1, 64), (2, 32), (0, 32), (0, 64), (3, 32), (3, 64),
-                                                                                                                    (4, 32), (4, 64)))
+                                                                                                                    (4, 32), (4, 64), (4, 128)))
 
     @property
     def search_preferred(self):
-        """the persistent launch is the faster form, so fused_search=None takes it: every network with one except gobang's, whose persistent
-        launch spills (1-2 KB of scratch per lane: the exact heads' 113 k-steps) and measured 2-100x slower than the launch-per-phase
-        loop at 128-2048 games (profiles/gobang_throughput.json)"""
+        """the persistent launch is the faster form, so fused_search=None takes it: every network with one except gobang's.  Gobang x
+        {32, 64}: the launch spills (1-2 KB of scratch per lane: the unrolled exact heads' 113 k-steps) and measured 2-100x slower than the
+        launch-per-phase loop at 128-2048 games (profiles/gobang_throughput.json).  Gobang x 128 (streamed heads, 672 B/lane): its A/B
+        against the per-phase loop (tools/gobang_throughput.py --nets gobang_128x8) has NOT been measured yet, so the flag stays false --
+        it turns true only on a measurement that shows the persistent form faster at 128, 512 and 2048 games by more than the spread
+        (DESIGN.md 7c); fused_search=True takes the launch meanwhile."""
         return self.can_search and self.game != 4
 
     def search(self, engine, sims, exact=False):

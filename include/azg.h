@@ -314,7 +314,10 @@ int  azg_search_wide_f16(azg_engine *e, void *stream, const void *w_packed_dev, 
  * and the next tree phase takes the softmax over all A, masks and renormalises.  Results are identical to `sims` x [azg_select /
  * azg_backup_select_logits, azg_resnet_tower_features_f16 + azg_policy_value_heads_fact_f16 (logits only)] + a final
  * azg_backup_select_logits without select, i.e. to the reference's evaluation fed NNetWrapper.process.  sims == 0: one-time setup only.
- * The engine's size picks the tile like azg_search_wide_f16 (games per workgroup). */
+ * The engine's size picks the tile like azg_search_wide_f16 (games per workgroup).  (game, channels) pairs: brandubh x 64, the 3-player env
+ * x 32, connect4 x {32, 64}, othello x {32, 64}, gobang x {32, 64, 128} -- gobang only here (no sparse heads), one game per workgroup; its
+ * 128-channel tile (the 128 x 8 net of envs/gobang/train.py) streams the heads' fragments through a short register ring and takes one
+ * workgroup of twelve wavefronts per CU; a tower too deep for the LDS beside the 15x15 image is refused with AZG_E_INVALID_ARG. */
 int  azg_search_wide_exact_f16(azg_engine *e, void *stream, const void *w_packed_dev, const float *bias_dev, const float *pre_scale_dev,
                                const float *pre_shift_dev, int nblocks, int channels, const void *head1_w_packed_dev,
                                const float *head1_b_dev, const void *wps_packed_dev, const void *wv_packed_dev, const float *head_b_dev,
@@ -405,7 +408,7 @@ int  azg_search_arena_f16(azg_engine *e, void *stream, int nmodels, const void *
                           const float *const *head_b_dev, const int32_t *p2i_host, const uint32_t *seat_of_slot_dev, int sims);
 
 /* The same for factorised-head networks (the pairs of azg_search_wide_exact_f16: brandubh x 64, the 3-player env x 32, connect4 x {32, 64},
- * othello x {32, 64}) on arena engines: one game per workgroup, `sims` x [find_leaf on the MOVER's tree, the MOVER's model -- tower, 1x1
+ * othello x {32, 64}, gobang x {32, 64, 128}) on arena engines: one game per workgroup, `sims` x [find_leaf on the MOVER's tree, the MOVER's model -- tower, 1x1
  * head convolutions and ALL A + P+1 logits, what NNetWrapper.process returns --, process_results].  Model m's parameters as
  * azg_search_wide_exact_f16 takes them, in entry m of each array.  A model whose pointers are ALL null is a raw seat (RawMCTSPlayer.process:
  * policy float32(1 / A) for every action, value zeros; no network runs for its games).  Seating as azg_search_arena_f16.  Results identical

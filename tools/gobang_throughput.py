@@ -1,8 +1,11 @@
 """Gobang self-play throughput on one GPU: the persistent search launch (azg_search_wide_exact_f16, one launch per move) against the
 launch-per-phase loop (azg_select -> NNetWrapper.process on the 15x15 HIP tower -> azg_backup per simulation) at the same size, for the
-reference's default 32 x 4 net and a 64 x 4 net, and the per-phase loop alone for envs/gobang/train.py's 128 x 8 net (no persistent
-launch), at several game counts.  Each case is measured `--reps` times, the two forms alternating, and the median kept.
-Prints one JSON line per case and writes them all to profiles/gobang_throughput.json.  Kernel averages: run it under the profiler, e.g.
+reference's default 32 x 4 net, a 64 x 4 net and envs/gobang/train.py's 128 x 8 net, at several game counts (`--nets` picks some of
+them).  Each case is measured `--reps` times, the two forms alternating, and the median kept with the spread (min, max).
+Prints one JSON line per case and writes them all to `--out` (default profiles/gobang_throughput.json, the record of the 32 x 4 and
+64 x 4 A/B and of the 128 x 8 per-phase baseline; the 128 x 8 net's A/B of its persistent launch is meant to go to
+profiles/gobang128_throughput.json: --nets gobang_128x8 --out profiles/gobang128_throughput.json).  Kernel averages: run it under the
+profiler, e.g.
 
     rocprofv3 --kernel-trace --stats --output-format csv -d profiles/gobang_rocprof -o gobang -- python tools/gobang_throughput.py
 """
@@ -62,10 +65,13 @@ def main():
     ap.add_argument('--sims', type=int, default=50)
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--games', type=int, nargs='+', default=[128, 512, 2048])
+    ap.add_argument('--nets', nargs='+', default=[n for n, _ in NETS], choices=[n for n, _ in NETS])
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'gobang_throughput.json'))
     a = ap.parse_args()
     rows = []
     for net_name, args in NETS:
+        if net_name not in a.nets:
+            continue
         torch.manual_seed(0)
         net = NNetWrapper(Game, args, device='cuda:0').refresh()
         assert net._hip is not None
