@@ -11,6 +11,7 @@ ABI_VERSION = 7
 
 GAME_CONNECT4, GAME_BRANDUBH, GAME_TRIMOK, GAME_OTHELLO, GAME_GOBANG = 0, 1, 2, 3, 4
 E_INVALID_ARG, E_HIP, E_INVALID_ACTION, E_TREE_FULL, E_EXAMPLES_FULL, E_UNSUPPORTED, E_INTERNAL, E_FLOATING_POINT = -1, -2, -3, -4, -5, -6, -7, -8
+SUPPORT_TOWER, SUPPORT_SEARCH_WIDE, SUPPORT_SEARCH_SPARSE, SUPPORT_SEARCH_FUSED = 1, 2, 4, 8      # azg_launch_support
 ERROR_NAMES = {-1: 'AZG_E_INVALID_ARG', -2: 'AZG_E_HIP', -3: 'AZG_E_INVALID_ACTION', -4: 'AZG_E_TREE_FULL',
                -5: 'AZG_E_EXAMPLES_FULL', -6: 'AZG_E_UNSUPPORTED', -7: 'AZG_E_INTERNAL', -8: 'AZG_E_FLOATING_POINT'}
 
@@ -97,6 +98,7 @@ SYMBOLS = {
     'azg_search_f16': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i]),
     'azg_policy_value_heads_f16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'azg_tower_layout': (_i, [_i, _i, _i, _vp, _vp, _vp]),
+    'azg_launch_support': (_i, [_i, _i]),
     'azg_resnet_tower_features_f16': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i]),
     'azg_policy_value_heads_fact_f16': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'azg_search_arena_f16': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
@@ -140,7 +142,11 @@ def lib():
         pass
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in SYMBOLS.items():
-        fn = getattr(L, name)
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            raise ImportError('%s does not export %s: it was built from older sources -- rebuild it '
+                              '(`python -m alphazero_general_amd.build --force`)' % (LIB_PATH, name)) from None
         fn.restype, fn.argtypes = res, args
     if L.azg_abi_version() != ABI_VERSION:
         raise ImportError('libazg_hip.so ABI version mismatch')
@@ -161,6 +167,13 @@ def game_info(game):
     gi = GameInfo()
     check(lib().azg_game_info_get(game, C.byref(gi)))
     return gi
+
+
+def launch_support(game, channels):
+    """the AZG_SUPPORT_* mask of (game id, tower width): which launches the library instantiates (0: none, also for no / an unknown game)"""
+    if game is None:
+        return 0
+    return max(lib().azg_launch_support(int(game), int(channels)), 0)
 
 
 def states_array(n):

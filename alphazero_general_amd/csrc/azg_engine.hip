@@ -11,6 +11,7 @@
 #include <vector>
 #include "azg_kernels.h"
 #include "azg_conv.h"
+#include "azg_tiles.h"
 
 using namespace azg;
 
@@ -109,6 +110,12 @@ template <typename T> static int dalloc(azg_engine *e, T **p, size_t count) {
     case AZG_GAME_OTHELLO: { using G = OT; CALL; } break; \
     case AZG_GAME_GOBANG: return fail(AZG_E_UNSUPPORTED, "no sparse heads for gobang (use the dense heads)"); \
     default: return fail(AZG_E_UNSUPPORTED, "game has no device rules"); }
+// dispatch on the observation format the tree kernels write (obs_dtype 0: f32 planes, 1: f16 planes, 2: f16 NHWC8 rows): CALL sees the
+// element type OBS, the flag NHWC8 and the buffer as OBS *o
+#define OBS_SWITCH(obs_dtype, obs, CALL) \
+    if ((obs_dtype) == 0) { using OBS = float; constexpr bool NHWC8 = false; OBS *const o = (OBS *)(obs); CALL; } \
+    else if ((obs_dtype) == 1) { using OBS = _Float16; constexpr bool NHWC8 = false; OBS *const o = (OBS *)(obs); CALL; } \
+    else { using OBS = _Float16; constexpr bool NHWC8 = true; OBS *const o = (OBS *)(obs); CALL; }
 
 static void prof_begin(azg_engine *e, hipStream_t s, int fam, EvPair &p) {
     if (!e->profile) return;
@@ -278,9 +285,7 @@ extern "C" int azg_select(azg_engine *e, void *stream, void *obs, int obs_dtype,
     if (obs_dtype < 0 || obs_dtype > 2) return fail(AZG_E_INVALID_ARG, "obs_dtype must be 0 (f32), 1 (f16) or 2 (f16 NHWC8)");
     hipStream_t s = (hipStream_t)stream;
     EvPair p; prof_begin(e, s, 0, p);
-    if (obs_dtype == 0) { GAME_SWITCH(e, AZG_LAUNCH((k_select<G, float>), dim3(e->v.B), dim3(64), 0, s, e->v, (float *)obs, row_of_slot)); }
-    else if (obs_dtype == 1) { GAME_SWITCH(e, AZG_LAUNCH((k_select<G, _Float16>), dim3(e->v.B), dim3(64), 0, s, e->v, (_Float16 *)obs, row_of_slot)); }
-    else { GAME_SWITCH(e, AZG_LAUNCH((k_select<G, _Float16, true>), dim3(e->v.B), dim3(64), 0, s, e->v, (_Float16 *)obs, row_of_slot)); }
+    OBS_SWITCH(obs_dtype, obs, GAME_SWITCH(e, AZG_LAUNCH((k_select<G, OBS, NHWC8>), dim3(e->v.B), dim3(64), 0, s, e->v, o, row_of_slot)));
     prof_end(e, s, 0, p);
     HIPCHK(hipGetLastError());
     return AZG_OK;
@@ -326,9 +331,7 @@ extern "C" int azg_backup_select(azg_engine *e, void *stream, const float *polic
     if (flags >= 0) { v.add_noise = (flags & AZG_FLAG_NOISE) ? 1 : 0; v.add_temp = (flags & AZG_FLAG_TEMP) ? 1 : 0; }
     EvPair p; prof_begin(e, s, 1, p);
     const int A = e->gi.action_size;
-    if (obs_dtype == 0) { GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, float, false, IN_PROBS>), dim3(v.B), dim3(128), 0, s, v, policy, value, A, (float *)obs, row_of_slot, 1, HeadRows{})); }
-    else if (obs_dtype == 1) { GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, _Float16, false, IN_PROBS>), dim3(v.B), dim3(128), 0, s, v, policy, value, A, (_Float16 *)obs, row_of_slot, 1, HeadRows{})); }
-    else { GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, _Float16, true, IN_PROBS>), dim3(v.B), dim3(128), 0, s, v, policy, value, A, (_Float16 *)obs, row_of_slot, 1, HeadRows{})); }
+    OBS_SWITCH(obs_dtype, obs, GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, OBS, NHWC8, IN_PROBS>), dim3(v.B), dim3(128), 0, s, v, policy, value, A, o, row_of_slot, 1, HeadRows{})));
     prof_end(e, s, 1, p);
     HIPCHK(hipGetLastError());
     return AZG_OK;
@@ -345,9 +348,7 @@ extern "C" int azg_backup_select_logits(azg_engine *e, void *stream, const float
     if (flags >= 0) { v.add_noise = (flags & AZG_FLAG_NOISE) ? 1 : 0; v.add_temp = (flags & AZG_FLAG_TEMP) ? 1 : 0; }
     EvPair p; prof_begin(e, s, 1, p);
     const float *nov = nullptr;
-    if (obs_dtype == 0) { GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, float, false, IN_LOGITS>), dim3(v.B), dim3(128), 0, s, v, logits, nov, logits_stride, (float *)obs, row_of_slot, do_select, HeadRows{})); }
-    else if (obs_dtype == 1) { GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, _Float16, false, IN_LOGITS>), dim3(v.B), dim3(128), 0, s, v, logits, nov, logits_stride, (_Float16 *)obs, row_of_slot, do_select, HeadRows{})); }
-    else { GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, _Float16, true, IN_LOGITS>), dim3(v.B), dim3(128), 0, s, v, logits, nov, logits_stride, (_Float16 *)obs, row_of_slot, do_select, HeadRows{})); }
+    OBS_SWITCH(obs_dtype, obs, GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, OBS, NHWC8, IN_LOGITS>), dim3(v.B), dim3(128), 0, s, v, logits, nov, logits_stride, o, row_of_slot, do_select, HeadRows{})));
     prof_end(e, s, 1, p);
     HIPCHK(hipGetLastError());
     return AZG_OK;
@@ -367,9 +368,7 @@ extern "C" int azg_backup_select_features(azg_engine *e, void *stream, const voi
     if (feat_k != want) return fail(AZG_E_INVALID_ARG, "feat_k must be cells x 16 rounded up to a multiple of 32 for this game");
     EvPair p; prof_begin(e, s, 1, p);
     const float *nov = nullptr, *f = (const float *)feat;
-    if (obs_dtype == 0) { SPARSE_GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, float, false, IN_FEATURES>), dim3(v.B), dim3(128), 0, s, v, f, nov, 0, (float *)obs, row_of_slot, do_select, hd)); }
-    else if (obs_dtype == 1) { SPARSE_GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, _Float16, false, IN_FEATURES>), dim3(v.B), dim3(128), 0, s, v, f, nov, 0, (_Float16 *)obs, row_of_slot, do_select, hd)); }
-    else { SPARSE_GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, _Float16, true, IN_FEATURES>), dim3(v.B), dim3(128), 0, s, v, f, nov, 0, (_Float16 *)obs, row_of_slot, do_select, hd)); }
+    OBS_SWITCH(obs_dtype, obs, SPARSE_GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, OBS, NHWC8, IN_FEATURES>), dim3(v.B), dim3(128), 0, s, v, f, nov, 0, o, row_of_slot, do_select, hd)));
     prof_end(e, s, 1, p);
     HIPCHK(hipGetLastError());
     return AZG_OK;
@@ -962,9 +961,20 @@ static int device_cus(int *cus) {
     return AZG_OK;
 }
 
+// the launch half of dispatch_tower: the row of AZG_TOWER_TILES that is (game, channels, bt, psplit, ksplit)
+static int tower_tile_launch(hipStream_t s, int game, int channels, int bt, int psplit, int ksplit, const TowerParams &P) {
+#define AZG_ROW(G, C, BT, PS, KS) \
+    if (game == G::ID && channels == C && bt == BT && psplit == PS && ksplit == KS) return launch_tower<G::H, G::W, BT, C, PS, NoSearch, KS>(s, P);
+    AZG_TOWER_TILES(AZG_ROW)
+#undef AZG_ROW
+    return fail(AZG_E_UNSUPPORTED, "no MFMA tower for this game / channel count (azg_launch_support: the pairs with AZG_SUPPORT_TOWER)");
+}
+
 // Boards per workgroup tile: the big tile has the least MFMA padding, small ones fill the chip at small batches (the arena,
 // the single-tree API, brandubh's 512 games per GPU).  Tuning builds (hipcc -DAZG_TUNING, tools/sweep_small.py) let the
 // environment override the choice: AZG_TOWER_BOARDS, AZG_TOWER_PSPLIT; the product library reads no environment.
+// This is the policy half: it picks (boards per tile, PSPLIT, KSPLIT) among the pair's rows of AZG_TOWER_TILES (an override
+// that names no row falls to the pair's largest tile); tower_tile_launch launches the row.
 static int dispatch_tower(hipStream_t s, int game, int channels, const TowerParams &P) {
 #ifdef AZG_TUNING
     static const int forced = getenv("AZG_TOWER_BOARDS") ? atoi(getenv("AZG_TOWER_BOARDS")) : 0;
@@ -976,63 +986,52 @@ static int dispatch_tower(hipStream_t s, int game, int channels, const TowerPara
     // (tile thresholds in boards per CU of THIS device -- measured on 256 CUs: 640 / 1280 boards = 2.5 / 5 per CU ... -- not in boards)
     int cus = 1;
     { const int r = device_cus(&cus); if (r != AZG_OK) return r; }
+    int bt = 0, ps = 1, ks = 1;                                      // (bt == 0: a pair without a tower -- no row matches)
     if (game == AZG_GAME_CONNECT4 && channels == 128) {
-        const int bt = forced ? forced : 2 * n <= 5 * cus ? 1 : n <= 5 * cus ? 2 : 4;
-        if (bt == 1 && psplit == 2) return launch_tower<C4::H, C4::W, 1, 128, 2>(s, P);   // 8 waves, 2 + 1 pixel subtiles: measured slower (101 vs 69 us)
-        if (bt == 1) return launch_tower<C4::H, C4::W, 1, 128>(s, P);
-#ifdef AZG_TUNING
-        if (bt == 2 && psplit == 2) return launch_tower<C4::H, C4::W, 2, 128, 2>(s, P);   // (sweep only: profiles/r03_arena_tile_sweep.txt)
-#endif
-        if (bt == 2) return launch_tower<C4::H, C4::W, 2, 128>(s, P);
-        return launch_tower<C4::H, C4::W, 4, 128>(s, P);
-    }
-    if (game == AZG_GAME_CONNECT4 && channels == 64) return launch_tower<C4::H, C4::W, 4, 64>(s, P);
-    if (game == AZG_GAME_CONNECT4 && channels == 32) {           // the default net of Coach.py:108-116 (BASELINE config 1): one cout group,
-        const int bt = forced ? forced : n <= 4 * cus ? 2 : 4;   // the tile's pixel subtiles dealt to two waves
-        if (bt == 2) return launch_tower<C4::H, C4::W, 2, 32, 2>(s, P);
-        return launch_tower<C4::H, C4::W, 4, 32, 2>(s, P);
-    }
-    if (game == AZG_GAME_BRANDUBH && channels == 64) {           // two cout groups: split the pixels too at small batches
+        bt = forced ? forced : 2 * n <= 5 * cus ? 1 : n <= 5 * cus ? 2 : 4;
+        if (bt != 1 && bt != 2) bt = 4;
+        if (psplit == 2 && bt != 4) ps = 2;                          // (an override only: the split 2-board tile exists in tuning builds alone)
+    } else if (game == AZG_GAME_CONNECT4 && channels == 64) {
+        bt = 4;
+    } else if ((game == AZG_GAME_CONNECT4 || game == AZG_GAME_OTHELLO) && channels == 32) {
+        bt = forced ? forced : n <= 4 * cus ? 2 : 4;
+        if (bt != 2) bt = 4;
+        ps = 2;
+    } else if (game == AZG_GAME_BRANDUBH && channels == 64) {
         // measured (us per evaluation incl. heads, 256 / 512 / 1024 / 2048 boards): 1 board, no split 39 / 47 / 66 / 107;
         // 1 board, split 35 / 46 / 80 / 113; 2 boards, split 39 / 43 / 63 / 113
         // round 3, the k-split 1-board tile (`sp == 3`): 28 / 36 / 64 / 114 -- the shape up to 512 boards
-        const int bt = forced ? forced : n <= 2 * cus ? 1 : 2;
+        bt = forced ? forced : n <= 2 * cus ? 1 : 2;
         const int sp = psplit ? psplit : n <= 2 * cus ? 3 : n <= 4 * cus ? 2 : 1;
-        if (bt == 1 && sp == 3) return launch_tower<BR::H, BR::W, 1, 64, 1, NoSearch, 2>(s, P);   // k-split: 4 waves = (cout group, k group)
-        if (bt == 1 && sp == 2) return launch_tower<BR::H, BR::W, 1, 64, 2>(s, P);
-        if (bt == 1) return launch_tower<BR::H, BR::W, 1, 64>(s, P);
-        if (sp == 2) return launch_tower<BR::H, BR::W, 2, 64, 2>(s, P);
-        return launch_tower<BR::H, BR::W, 2, 64>(s, P);
-    }
-    if (game == AZG_GAME_BRANDUBH && channels == 128) return launch_tower<BR::H, BR::W, 2, 128>(s, P);
-    if (game == AZG_GAME_TRIMOK && channels == 32) {             // one cout group
-        const int bt = forced ? forced : n <= 8 * cus ? 2 : 5;
-        const int sp = psplit ? psplit : 2;                      // (256 boards: 26 us unsplit, 23 us split in two)
-        if (bt == 2 && sp == 4) return launch_tower<TM::H, TM::W, 2, 32, 4>(s, P);
-        if (bt == 2 && sp == 2) return launch_tower<TM::H, TM::W, 2, 32, 2>(s, P);
-        if (bt == 2) return launch_tower<TM::H, TM::W, 2, 32>(s, P);
-        return launch_tower<TM::H, TM::W, 5, 32>(s, P);
-    }
-    // othello: an 8x8 board is exactly four pixel subtiles, so no tile carries pad rows; the tiles of the widths it shares with connect4's
-    // default net (32) and brandubh's (64)
-    if (game == AZG_GAME_OTHELLO && channels == 32) {            // one cout group, the tile's pixel subtiles dealt to two waves
-        const int bt = forced ? forced : n <= 4 * cus ? 2 : 4;
-        if (bt == 2) return launch_tower<OT::H, OT::W, 2, 32, 2>(s, P);
-        return launch_tower<OT::H, OT::W, 4, 32, 2>(s, P);
-    }
-    if (game == AZG_GAME_OTHELLO && channels == 64) {            // two cout groups: the k-split 1-board tile at small batches, as brandubh
-        const int bt = forced ? forced : n <= 2 * cus ? 1 : 2;
+        if (bt != 1) bt = 2;
+        if (bt == 1 && sp == 3) ks = 2; else if (sp == 2) ps = 2;
+    } else if (game == AZG_GAME_BRANDUBH && channels == 128) {
+        bt = 2;
+    } else if (game == AZG_GAME_TRIMOK && channels == 32) {
+        bt = forced ? forced : n <= 8 * cus ? 2 : 5;
+        const int sp = psplit ? psplit : 2;                          // (256 boards: 26 us unsplit, 23 us split in two)
+        if (bt != 2) bt = 5; else if (sp == 2 || sp == 4) ps = sp;
+    } else if (game == AZG_GAME_OTHELLO && channels == 64) {         // the k-split 1-board tile at small batches, as brandubh
+        bt = forced ? forced : n <= 2 * cus ? 1 : 2;
         const int sp = psplit ? psplit : n <= 2 * cus ? 3 : n <= 4 * cus ? 2 : 1;
-        if (bt == 1) return launch_tower<OT::H, OT::W, 1, 64, 1, NoSearch, 2>(s, P);
-        if (sp == 2) return launch_tower<OT::H, OT::W, 2, 64, 2>(s, P);
-        return launch_tower<OT::H, OT::W, 2, 64>(s, P);
+        if (bt == 1) ks = 2; else { bt = 2; if (sp == 2) ps = 2; }
+    } else if (game == AZG_GAME_GOBANG) {                            // one board per tile, three pixel groups, at every width
+        bt = 1; ps = 3;
     }
-    // gobang: a 15x15 board is 225 pixels, 15 pixel subtiles (15 spare lanes, five border classes) -- an odd count, so no k-split; one
-    // board per tile, its subtiles dealt to three pixel groups of five (every width: 3, 6 or 12 waves)
-    if (game == AZG_GAME_GOBANG && channels == 32) return launch_tower<GB::H, GB::W, 1, 32, 3>(s, P);
-    if (game == AZG_GAME_GOBANG && channels == 64) return launch_tower<GB::H, GB::W, 1, 64, 3>(s, P);
-    if (game == AZG_GAME_GOBANG && channels == 128) return launch_tower<GB::H, GB::W, 1, 128, 3>(s, P);
-    return fail(AZG_E_UNSUPPORTED, "no MFMA tower for this game / channel count (supported: connect4 x {32,64,128}, brandubh x {64,128}, trimok x 32, othello x {32,64}, gobang x {32,64,128} channels)");
+    return tower_tile_launch(s, game, channels, bt, ps, ks, P);
+}
+
+// TowerParams by name: the tower's own fields; a launch then sets the heads it has, everything else stays null / 0
+static TowerParams tower_params(const void *x, const void *w, const float *bias, const float *pre_scale, const float *pre_shift, int boards, int nblocks) {
+    TowerParams P{};
+    P.x = x; P.w = w; P.bias = bias; P.pre_scale = pre_scale; P.pre_shift = pre_shift; P.boards = boards; P.nblocks = nblocks;
+    return P;
+}
+static void set_fused_heads(TowerParams &P, const void *head_w, const float *head_b, float *policy, float *value, int A, int NV) {
+    P.head_w = head_w; P.head_b = head_b; P.policy = policy; P.value = value; P.A = A; P.NV = NV;
+}
+static void set_fact_heads(TowerParams &P, const void *head1_w, const float *head1_b, void *feat, int feat_k) {
+    P.head1_w = head1_w; P.head1_b = head1_b; P.feat = feat; P.feat_k = feat_k;
 }
 
 // [boards, C, H*W] f32 planes (what GameState.observation / the reference's batch tensors hold) -> the tower's input rows [boards * H*W][8] fp16
@@ -1056,7 +1055,7 @@ extern "C" int azg_resnet_tower_f16(void *stream, int game, const void *x, const
                                     const float *pre_shift, void *y, int boards, int nblocks, int channels) {
     if (!x || !w || !bias || !y || boards <= 0 || nblocks < 0) return fail(AZG_E_INVALID_ARG, "null argument");
     if (nblocks > 0 && (!pre_scale || !pre_shift)) return fail(AZG_E_INVALID_ARG, "pre_scale/pre_shift required");
-    TowerParams P{x, w, bias, pre_scale, pre_shift, y, boards, nblocks, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, {}};
+    TowerParams P = tower_params(x, w, bias, pre_scale, pre_shift, boards, nblocks); P.y = y;
     EvPair ep; const bool prof = netprof_begin((hipStream_t)stream, ep);
     const int r = dispatch_tower((hipStream_t)stream, game, channels, P);
     netprof_end((hipStream_t)stream, 0, prof, ep);
@@ -1069,8 +1068,8 @@ extern "C" int azg_resnet_tower_features_f16(void *stream, int game, const void 
     if (!x || !w || !bias || !head1_w || !head1_b || !feat || boards <= 0 || nblocks < 0) return fail(AZG_E_INVALID_ARG, "null argument");
     if (nblocks > 0 && (!pre_scale || !pre_shift)) return fail(AZG_E_INVALID_ARG, "pre_scale/pre_shift required");
     if (feat_k <= 0 || (feat_k & 31)) return fail(AZG_E_INVALID_ARG, "feat_k must be a positive multiple of 32");
-    TowerParams P{x, w, bias, pre_scale, pre_shift, nullptr, boards, nblocks, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, head1_w, head1_b, feat, feat_k,
-                  nullptr, 0, {}};
+    TowerParams P = tower_params(x, w, bias, pre_scale, pre_shift, boards, nblocks);
+    set_fact_heads(P, head1_w, head1_b, feat, feat_k);
     EvPair ep; const bool prof = netprof_begin((hipStream_t)stream, ep);
     const int r = dispatch_tower((hipStream_t)stream, game, channels, P);
     netprof_end((hipStream_t)stream, 0, prof, ep);
@@ -1083,7 +1082,8 @@ extern "C" int azg_resnet_policy_value_f16(void *stream, int game, const void *x
     if (!x || !w || !bias || !head_w || !head_b || !policy || !value || boards <= 0 || nblocks < 0) return fail(AZG_E_INVALID_ARG, "null argument");
     if (A <= 0 || NV <= 0 || A + NV > 16) return fail(AZG_E_UNSUPPORTED, "fused heads need A + NV <= 16");
     if (nblocks > 0 && (!pre_scale || !pre_shift)) return fail(AZG_E_INVALID_ARG, "pre_scale/pre_shift required");
-    TowerParams P{x, w, bias, pre_scale, pre_shift, nullptr, boards, nblocks, head_w, head_b, policy, value, A, NV, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, {}};
+    TowerParams P = tower_params(x, w, bias, pre_scale, pre_shift, boards, nblocks);
+    set_fused_heads(P, head_w, head_b, policy, value, A, NV);
     EvPair ep; const bool prof = netprof_begin((hipStream_t)stream, ep);
     const int r = dispatch_tower((hipStream_t)stream, game, 128, P);
     netprof_end((hipStream_t)stream, 0, prof, ep);
@@ -1102,8 +1102,8 @@ extern "C" int azg_resnet_policy_value_multi_f16(void *stream, int game, const v
     for (int m = 0; m < nmodels; m++)
         if (!w[m] || !bias[m] || !head_w[m] || !head_b[m] || (nblocks > 0 && (!pre_scale[m] || !pre_shift[m]))) return fail(AZG_E_INVALID_ARG, "null model parameter");
     // the grid is sized for max_boards rows plus one partial tile per extra model
-    TowerParams P{x, w[0], bias[0], nblocks ? pre_scale[0] : nullptr, nblocks ? pre_shift[0] : nullptr, nullptr, max_boards, nblocks,
-                  head_w[0], head_b[0], policy, value, A, NV, nullptr, nullptr, nullptr, nullptr, 0, rows_per_model, nmodels, {}};
+    TowerParams P = tower_params(x, w[0], bias[0], nblocks ? pre_scale[0] : nullptr, nblocks ? pre_shift[0] : nullptr, max_boards, nblocks);
+    set_fused_heads(P, head_w[0], head_b[0], policy, value, A, NV); P.rows_per_model = rows_per_model; P.nmodels = nmodels;
     for (int m = 1; m < nmodels; m++)
         P.alt[m - 1] = TowerParams::Model{w[m], bias[m], nblocks ? pre_scale[m] : nullptr, nblocks ? pre_shift[m] : nullptr, head_w[m], head_b[m]};
     EvPair ep; const bool prof = netprof_begin((hipStream_t)stream, ep);
@@ -1119,7 +1119,8 @@ extern "C" int azg_search_f16(azg_engine *e, void *stream, const void *w, const 
     if (e->cfg.game != AZG_GAME_CONNECT4 || e->v.arena)
         return fail(AZG_E_UNSUPPORTED, "the fused search kernel is built for connect4 self-play with a 128-channel tower (use azg_select / network / azg_backup)");
     const int A = e->gi.action_size, NV = e->gi.num_players + 1;
-    TowerParams P{nullptr, w, bias, pre_scale, pre_shift, nullptr, e->v.B, nblocks, head_w, head_b, nullptr, nullptr, A, NV, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, {}};
+    TowerParams P = tower_params(nullptr, w, bias, pre_scale, pre_shift, e->v.B, nblocks);
+    set_fused_heads(P, head_w, head_b, nullptr, nullptr, A, NV);
     SearchArgs<C4> sa{e->v, sims};
     EvPair ep; const bool prof = sims > 0 && netprof_begin((hipStream_t)stream, ep);
     // games per workgroup like the stand-alone tower's tile (dispatch_tower): small engines -- the single-tree MCTS class, config 1's 32 games --
@@ -1143,8 +1144,8 @@ extern "C" int azg_search_arena_f16(azg_engine *e, void *stream, int nmodels, co
     for (int m = 0; m < nmodels; m++)
         if (!w[m] || !bias[m] || !head_w[m] || !head_b[m] || (nblocks > 0 && (!pre_scale || !pre_shift || !pre_scale[m] || !pre_shift[m]))) return fail(AZG_E_INVALID_ARG, "null model parameter");
     const int A = e->gi.action_size, NV = e->gi.num_players + 1;
-    TowerParams P{nullptr, w[0], bias[0], nblocks ? pre_scale[0] : nullptr, nblocks ? pre_shift[0] : nullptr, nullptr, e->v.B, nblocks,
-                  head_w[0], head_b[0], nullptr, nullptr, A, NV, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nmodels, {}};
+    TowerParams P = tower_params(nullptr, w[0], bias[0], nblocks ? pre_scale[0] : nullptr, nblocks ? pre_shift[0] : nullptr, e->v.B, nblocks);
+    set_fused_heads(P, head_w[0], head_b[0], nullptr, nullptr, A, NV); P.nmodels = nmodels;
     for (int m = 1; m < nmodels; m++)
         P.alt[m - 1] = TowerParams::Model{w[m], bias[m], nblocks ? pre_scale[m] : nullptr, nblocks ? pre_shift[m] : nullptr, head_w[m], head_b[m]};
     SearchArena<C4> sa{e->v, sims, SeatMap{}, seat_of_slot};
@@ -1165,70 +1166,31 @@ static int wide_forced_tile() { static const int f = getenv("AZG_WIDE_BOARDS") ?
 static constexpr int wide_forced_tile() { return 0; }
 #endif
 
-// ONE tile shape of the launch (bt games per workgroup) for (game, tower width); AZG_E_UNSUPPORTED: no such tile.  sparse heads (EXACT =
-// false: hd) or full-width heads (EXACT = true: hf).  init: one-time set-up only.  occ: see launch_tower.
+// ONE tile shape of the launch (bt games per workgroup) for (game, tower width): the row of AZG_WIDE_TILES; AZG_E_UNSUPPORTED: no such tile.
+// sparse heads (EXACT = false: hd; the pairs with has_sparse_heads only) or full-width heads (EXACT = true: hf).  init: one-time set-up
+// only.  occ: see launch_tower.
 template <bool EXACT>
 static int wide_tile_launch(azg_engine *e, hipStream_t s, const TowerParams &P, int channels, int bt, const HeadRows &hd, const HeadsFull &hf, int sims,
                             bool init, int *occ) {
     const int game = e->cfg.game;
-    if (game == AZG_GAME_BRANDUBH && channels == 64) {
-        // two workgroups of four wavefronts per CU in every shape
-        using SW = SearchWide<BR, 2, EXACT>;
-        const SW sa{e->v, sims, hd, hf};
-        if (bt == 1) return launch_tower<BR::H, BR::W, 1, 64, 1, SW, 2>(s, P, sa, init, occ);      // four wavefronts per game (walk, priors, masks, rules), k-split tower
-        if (bt == 2) return launch_tower<BR::H, BR::W, 2, 64, 2, SW>(s, P, sa, init, occ);         // walker + helper per game
-        if (bt == 3) return launch_tower<BR::H, BR::W, 3, 64, 2, SW>(s, P, sa, init, occ);         // solo tree phase: one wavefront per game
-        if (bt == 4) return launch_tower<BR::H, BR::W, 4, 64, 2, SW>(s, P, sa, init, occ);         // (two 4-game workgroups fill a CU's LDS with a 4-block tower's
-                                                                                                    //  parameters beside them: a deeper tower does not fit -> AZG_E_INVALID_ARG)
 #ifdef AZG_TUNING
-        if (bt == 8) return launch_tower<BR::H, BR::W, 8, 64, 4, SearchWide<BR, 1, EXACT>>(s, P, SearchWide<BR, 1, EXACT>{e->v, sims, hd, hf}, init, occ);   // one workgroup of eight wavefronts per CU
-        if (bt == 12) return launch_tower<BR::H, BR::W, 2, 64, 2, SearchWide<BR, 1, EXACT>, 2>(s, P, SearchWide<BR, 1, EXACT>{e->v, sims, hd, hf}, init, occ);  // 2 games, 8 wavefronts (k-split), one workgroup per CU
-        if (bt == 14) return launch_tower<BR::H, BR::W, 4, 64, 2, SearchWide<BR, 1, EXACT>>(s, P, SearchWide<BR, 1, EXACT>{e->v, sims, hd, hf}, init, occ);  // (what the spills cost: the 4-board tile with the whole register file)
-#endif
-    } else if (game == AZG_GAME_TRIMOK && channels == 32) {
-        if (bt == 1) return launch_tower<TM::H, TM::W, 1, 32, 2, SearchWide<TM, 1, EXACT>>(s, P, SearchWide<TM, 1, EXACT>{e->v, sims, hd, hf}, init, occ);
-        if (bt == 2) return launch_tower<TM::H, TM::W, 2, 32, 4, SearchWide<TM, 2, EXACT>>(s, P, SearchWide<TM, 2, EXACT>{e->v, sims, hd, hf}, init, occ);   // walker + helper per game
-#ifdef AZG_TUNING
-        if (bt == 4) return launch_tower<TM::H, TM::W, 4, 32, 4, SearchWide<TM, 2, EXACT>>(s, P, SearchWide<TM, 2, EXACT>{e->v, sims, hd, hf}, init, occ);
-#endif
-    } else if (game == AZG_GAME_CONNECT4 && channels == 32) {
-        // the reference's DEFAULT net (Coach.py:108-116: 32 channels x 4 blocks, 16 + 16 head channels -- BASELINE config 1's network and what an
-        // unconfigured Coach trains) on connect4: factorised heads, so the wide search mode; tiles like the 3-player env's 32-channel tower
-        if (bt == 1) return launch_tower<C4::H, C4::W, 1, 32, 2, SearchWide<C4, 1, EXACT>>(s, P, SearchWide<C4, 1, EXACT>{e->v, sims, hd, hf}, init, occ);
-        if (bt == 2) return launch_tower<C4::H, C4::W, 2, 32, 4, SearchWide<C4, 2, EXACT>>(s, P, SearchWide<C4, 2, EXACT>{e->v, sims, hd, hf}, init, occ);   // walker + helper per game
-    } else if (game == AZG_GAME_CONNECT4 && channels == 64) {
-        if (bt == 1) return launch_tower<C4::H, C4::W, 1, 64, 2, SearchWide<C4, 2, EXACT>>(s, P, SearchWide<C4, 2, EXACT>{e->v, sims, hd, hf}, init, occ);   // four wavefronts per game
-        if (bt == 2) return launch_tower<C4::H, C4::W, 2, 64, 2, SearchWide<C4, 2, EXACT>>(s, P, SearchWide<C4, 2, EXACT>{e->v, sims, hd, hf}, init, occ);   // walker + helper per game
-    } else if (game == AZG_GAME_OTHELLO && channels == 32) {
-        // the default net of an unconfigured Coach (32 x 4): connect4-32's shapes
-        if (bt == 1) return launch_tower<OT::H, OT::W, 1, 32, 2, SearchWide<OT, 1, EXACT>>(s, P, SearchWide<OT, 1, EXACT>{e->v, sims, hd, hf}, init, occ);
-        if (bt == 2) return launch_tower<OT::H, OT::W, 2, 32, 4, SearchWide<OT, 2, EXACT>>(s, P, SearchWide<OT, 2, EXACT>{e->v, sims, hd, hf}, init, occ);   // walker + helper per game
-    } else if (game == AZG_GAME_OTHELLO && channels == 64) {
-        // envs/othello/train.py's net (64 x 4, 16 + 16 head channels): brandubh-64's shapes, two workgroups of four wavefronts per CU
-        using SW = SearchWide<OT, 2, EXACT>;
+    if (game == AZG_GAME_BRANDUBH && channels == 64) {             // AZG_WIDE_BOARDS codes: one workgroup per CU
+        using SW = SearchWide<BR, 1, EXACT>;
         const SW sa{e->v, sims, hd, hf};
-        if (bt == 1) return launch_tower<OT::H, OT::W, 1, 64, 1, SW, 2>(s, P, sa, init, occ);      // k-split tower
-        if (bt == 2) return launch_tower<OT::H, OT::W, 2, 64, 2, SW>(s, P, sa, init, occ);
-        if (bt == 3) return launch_tower<OT::H, OT::W, 3, 64, 2, SW>(s, P, sa, init, occ);
-        if (bt == 4) return launch_tower<OT::H, OT::W, 4, 64, 2, SW>(s, P, sa, init, occ);
-    } else if (game == AZG_GAME_GOBANG && (channels == 32 || channels == 64 || channels == 128)) {
-        // the one-game tile of the stand-alone 15x15 towers (three pixel groups of five subtiles; walker, helper, mask wave and, from 64
-        // channels, the rules wave); exact heads only -- gobang has no sparse heads.  128 channels (envs/gobang/train.py's 128 x 8 net):
-        // twelve wavefronts, one workgroup per CU, the streamed heads loop (heads_full_stream)
-        if constexpr (EXACT) {
-            if (bt == 1 && channels == 128) return launch_tower<GB::H, GB::W, 1, 128, 3, SearchWide<GB, 1, EXACT>>(s, P, SearchWide<GB, 1, EXACT>{e->v, sims, hd, hf}, init, occ);
-            if (bt == 1 && channels == 32) return launch_tower<GB::H, GB::W, 1, 32, 3, SearchWide<GB, 1, EXACT>>(s, P, SearchWide<GB, 1, EXACT>{e->v, sims, hd, hf}, init, occ);
-            if (bt == 1 && channels == 64) return launch_tower<GB::H, GB::W, 1, 64, 3, SearchWide<GB, 1, EXACT>>(s, P, SearchWide<GB, 1, EXACT>{e->v, sims, hd, hf}, init, occ);
-        }
+        if (bt == 8) return launch_tower<BR::H, BR::W, 8, 64, 4, SW>(s, P, sa, init, occ);         // one workgroup of eight wavefronts per CU
+        if (bt == 12) return launch_tower<BR::H, BR::W, 2, 64, 2, SW, 2>(s, P, sa, init, occ);     // 2 games, 8 wavefronts (k-split), one workgroup per CU
+        if (bt == 14) return launch_tower<BR::H, BR::W, 4, 64, 2, SW>(s, P, sa, init, occ);        // (what the spills cost: the 4-board tile with the whole register file)
     }
+    if (game == AZG_GAME_TRIMOK && channels == 32 && bt == 4)
+        return launch_tower<TM::H, TM::W, 4, 32, 4, SearchWide<TM, 2, EXACT>>(s, P, SearchWide<TM, 2, EXACT>{e->v, sims, hd, hf}, init, occ);
+#endif
+#define AZG_ROW(G, C, BT, PS, MINB, KS) \
+    if constexpr (EXACT || has_sparse_heads<G>) if (game == G::ID && channels == C && bt == BT) { \
+        using SW = SearchWide<G, MINB, EXACT>; \
+        return launch_tower<G::H, G::W, BT, C, PS, SW, KS>(s, P, SW{e->v, sims, hd, hf}, init, occ); }
+    AZG_WIDE_TILES(AZG_ROW)
+#undef AZG_ROW
     return AZG_E_UNSUPPORTED;
-}
-
-static int wide_max_tile(int game, int channels) {
-    if ((game == AZG_GAME_BRANDUBH || game == AZG_GAME_OTHELLO) && channels == 64) return 4;
-    if (game == AZG_GAME_GOBANG && (channels == 32 || channels == 64 || channels == 128)) return 1;
-    if ((game == AZG_GAME_TRIMOK && channels == 32) || (game == AZG_GAME_CONNECT4 && (channels == 32 || channels == 64)) || (game == AZG_GAME_OTHELLO && channels == 32)) return 2;
-    return 0;
 }
 
 // The tile model (used when no measurement exists: a launch that is being captured without a set-up call before it).  Nothing in it is
@@ -1377,10 +1339,10 @@ static int search_wide(azg_engine *e, void *stream, const void *w, const float *
     const int A = e->gi.action_size, NV = e->gi.num_players + 1, hw = e->gi.obs_h * e->gi.obs_w;
     if (feat_k != (hw * 16 + 31) / 32 * 32) return fail(AZG_E_INVALID_ARG, "feat_k must be H*W*16 rounded up to 32");
     if (wide_max_tile(e->cfg.game, channels) == 0)
-        return fail(AZG_E_UNSUPPORTED, "persistent wide-head search: brandubh x 64, the 3-player env x 32, connect4 x {32, 64}, othello x {32, 64} and gobang x {32, 64, 128} channels (use azg_select / network / azg_backup)");
+        return fail(AZG_E_UNSUPPORTED, "persistent wide-head search: built for the pairs azg_launch_support gives AZG_SUPPORT_SEARCH_WIDE (use azg_select / network / azg_backup)");
     if (!EXACT && e->cfg.game == AZG_GAME_GOBANG) return fail(AZG_E_UNSUPPORTED, "no sparse heads for gobang (use the exact persistent launch)");
-    TowerParams P{nullptr, w, bias, pre_scale, pre_shift, nullptr, e->v.B, nblocks, nullptr, nullptr, nullptr, nullptr, A, NV, nullptr, head1_w, head1_b, nullptr, feat_k,
-                  nullptr, 0, {}};
+    TowerParams P = tower_params(nullptr, w, bias, pre_scale, pre_shift, e->v.B, nblocks);
+    set_fact_heads(P, head1_w, head1_b, nullptr, feat_k); P.A = A; P.NV = NV;
     hipStream_t s = (hipStream_t)stream;
     // Games per workgroup by the engine's size (SelfPlayAgent.pyx:23-26: the batch is whatever the caller made it): measured at set-up
     // (sims == 0) on this device with this network, else the device-derived model above.  More boards per tile share every weight fragment
@@ -1433,13 +1395,16 @@ extern "C" int azg_search_wide_exact_f16(azg_engine *e, void *stream, const void
                              HeadsFull{(const half8 *)wps_packed, (const half8 *)wv_packed, head_b}, feat_k, sims);
 }
 
-// the wide arena launch: the one-game tile of each (game, width) -- the self-play launch's bt == 1 shape (arena shards are small: the
-// default arenaCompare of 128 games is below the CU count), no tile autotune
-template <class G, int C, int PSPLIT, int MINB, int KSPLIT>
+// the wide arena launch: the one-game row of each (game, width) in AZG_WIDE_TILES -- the self-play launch's bt == 1 shape (arena shards
+// are small: the default arenaCompare of 128 games is below the CU count), no tile autotune
+template <class G, int C, int BT, int PSPLIT, int MINB, int KSPLIT>
 static int wide_arena_tile(hipStream_t s, const TowerParams &P, const WideArenaArgs &a, bool init) {
-    SearchWideArena<G, MINB> sa;
-    static_cast<WideArenaArgs &>(sa) = a;
-    return launch_tower<G::H, G::W, 1, C, PSPLIT, SearchWideArena<G, MINB>, KSPLIT>(s, P, sa, init);
+    if constexpr (BT == 1) {
+        SearchWideArena<G, MINB> sa;
+        static_cast<WideArenaArgs &>(sa) = a;
+        return launch_tower<G::H, G::W, 1, C, PSPLIT, SearchWideArena<G, MINB>, KSPLIT>(s, P, sa, init);
+    }
+    return AZG_E_UNSUPPORTED;
 }
 
 extern "C" int azg_search_arena_wide_exact_f16(azg_engine *e, void *stream, int nmodels, const void *const *w, const float *const *bias,
@@ -1451,8 +1416,8 @@ extern "C" int azg_search_arena_wide_exact_f16(azg_engine *e, void *stream, int 
         return fail(AZG_E_INVALID_ARG, "null or out-of-range argument");
     const int game = e->cfg.game;
     if (!e->v.arena || wide_max_tile(game, channels) == 0)
-        return fail(AZG_E_UNSUPPORTED, "the persistent wide arena launch is built for arena engines on brandubh x 64, the 3-player env x 32, connect4 x {32, 64} "
-                                       "othello x {32, 64} and gobang x {32, 64, 128} channels (use azg_select / network / azg_backup)");
+        return fail(AZG_E_UNSUPPORTED, "the persistent wide arena launch is built for arena engines on the pairs azg_launch_support gives "
+                                       "AZG_SUPPORT_SEARCH_WIDE (use azg_select / network / azg_backup)");
     if (nmodels < e->gi.num_players || nmodels > 4) return fail(AZG_E_INVALID_ARG, "one model per player, at most 4");
     const int A = e->gi.action_size, NV = e->gi.num_players + 1, hw = e->gi.obs_h * e->gi.obs_w;
     if (feat_k != (hw * 16 + 31) / 32 * 32) return fail(AZG_E_INVALID_ARG, "feat_k must be H*W*16 rounded up to 32");
@@ -1476,21 +1441,15 @@ extern "C" int azg_search_arena_wide_exact_f16(azg_engine *e, void *stream, int 
     }
     // (P: the shape of the launch -- boards, depth, heads form; the parameters every workgroup reads are its model's, sa.m)
     const WideModel &M0 = sa0.m[real < 0 ? 0 : real];
-    TowerParams P{nullptr, M0.w, M0.bias, M0.pre_scale, M0.pre_shift, nullptr, e->v.B, nblocks, nullptr, nullptr, nullptr, nullptr, A, NV, nullptr,
-                  M0.head1_w, M0.head1_b, nullptr, feat_k, nullptr, 0, {}};
+    TowerParams P = tower_params(nullptr, M0.w, M0.bias, M0.pre_scale, M0.pre_shift, e->v.B, nblocks);
+    set_fact_heads(P, M0.head1_w, M0.head1_b, nullptr, feat_k); P.A = A; P.NV = NV;
     hipStream_t s = (hipStream_t)stream;
     const bool init = sims == 0;                                  // sims == 0: set up only
     EvPair ep; const bool prof = !init && netprof_begin(s, ep);
     int r = AZG_E_UNSUPPORTED;
-    if (game == AZG_GAME_BRANDUBH && channels == 64) r = wide_arena_tile<BR, 64, 1, 2, 2>(s, P, sa0, init);
-    else if (game == AZG_GAME_TRIMOK && channels == 32) r = wide_arena_tile<TM, 32, 2, 1, 1>(s, P, sa0, init);
-    else if (game == AZG_GAME_CONNECT4 && channels == 32) r = wide_arena_tile<C4, 32, 2, 1, 1>(s, P, sa0, init);
-    else if (game == AZG_GAME_CONNECT4 && channels == 64) r = wide_arena_tile<C4, 64, 2, 2, 1>(s, P, sa0, init);
-    else if (game == AZG_GAME_OTHELLO && channels == 32) r = wide_arena_tile<OT, 32, 2, 1, 1>(s, P, sa0, init);
-    else if (game == AZG_GAME_OTHELLO && channels == 64) r = wide_arena_tile<OT, 64, 1, 2, 2>(s, P, sa0, init);
-    else if (game == AZG_GAME_GOBANG && channels == 32) r = wide_arena_tile<GB, 32, 3, 1, 1>(s, P, sa0, init);
-    else if (game == AZG_GAME_GOBANG && channels == 64) r = wide_arena_tile<GB, 64, 3, 1, 1>(s, P, sa0, init);
-    else if (game == AZG_GAME_GOBANG && channels == 128) r = wide_arena_tile<GB, 128, 3, 1, 1>(s, P, sa0, init);
+#define AZG_ROW(G, C, BT, PS, MINB, KS) if (BT == 1 && game == G::ID && channels == C) r = wide_arena_tile<G, C, BT, PS, MINB, KS>(s, P, sa0, init);
+    AZG_WIDE_TILES(AZG_ROW)
+#undef AZG_ROW
     if (r == AZG_E_UNSUPPORTED) { g_kev = nullptr; return fail(r, "persistent wide arena launch: no tile for this game / width"); }
     if (!init) netprof_end(s, 2, prof, ep);
     return r;
@@ -1545,27 +1504,18 @@ extern "C" int64_t azg_tower_weights_size(int channels, int nblocks) {
     return ((int64_t)STEM_KSTEPS + (int64_t)2 * nblocks * 9 * (channels / 32) + AZG_TOWER_W_SLACK_KSTEPS) * kstep;
 }
 
-// host-side layout tables of the tower (no device needed): the pixel -> (subtile, lane) map and the padded LDS row of every pixel
-template <int H, int W, int BOARDS, int C>
-static int tower_layout_of(int16_t *map, int32_t *qrow, int32_t *info) {
-    using GEO = TowerGeom<H, W, BOARDS, C>;
-    if (map && !tower_pixmap<GEO>(map)) return fail(AZG_E_INTERNAL, "tower pixel map does not fit its subtiles");
-    if (qrow) for (int p = 0; p < GEO::ROWS; p++) qrow[p] = GEO::qrow(p);
-    info[0] = GEO::NSUB; info[1] = GEO::ROWS; info[2] = GEO::RSTRIDE; info[3] = GEO::TROWS; info[4] = GEO::TILE; info[5] = GEO::PW;
-    info[6] = GEO::LEAD; info[7] = GEO::BSTRIDE;
-    return AZG_OK;
-}
-
+// host-side layout tables of one instantiated tile and the launches a (game, tower width) has: both straight from the tile lists (azg_tiles.h)
 extern "C" int azg_tower_layout(int game, int boards_per_tile, int channels, int16_t *pixmap, int32_t *qrow, int32_t *info8) {
     if (!info8) return fail(AZG_E_INVALID_ARG, "null argument");
-#define AZG_LAYOUT(GM, BT, CH) if (game == GM::ID && boards_per_tile == BT && channels == CH) return tower_layout_of<GM::H, GM::W, BT, CH>(pixmap, qrow, info8)
-    AZG_LAYOUT(C4, 1, 128); AZG_LAYOUT(C4, 2, 128); AZG_LAYOUT(C4, 4, 128); AZG_LAYOUT(C4, 4, 64); AZG_LAYOUT(C4, 2, 32); AZG_LAYOUT(C4, 4, 32);
-    AZG_LAYOUT(BR, 1, 64); AZG_LAYOUT(BR, 2, 64); AZG_LAYOUT(BR, 2, 128);
-    AZG_LAYOUT(TM, 2, 32); AZG_LAYOUT(TM, 5, 32);
-    AZG_LAYOUT(OT, 1, 32); AZG_LAYOUT(OT, 2, 32); AZG_LAYOUT(OT, 4, 32); AZG_LAYOUT(OT, 1, 64); AZG_LAYOUT(OT, 2, 64); AZG_LAYOUT(OT, 3, 64); AZG_LAYOUT(OT, 4, 64);
-    AZG_LAYOUT(GB, 1, 32); AZG_LAYOUT(GB, 1, 64); AZG_LAYOUT(GB, 1, 128);
-#undef AZG_LAYOUT
-    return fail(AZG_E_UNSUPPORTED, "no tower instantiation for this (game, boards per tile, channels)");
+    const int r = tower_layout(game, boards_per_tile, channels, pixmap, qrow, info8);
+    if (r == AZG_E_INTERNAL) return fail(r, "tower pixel map does not fit its subtiles");
+    if (r == AZG_E_UNSUPPORTED) return fail(r, "no tower instantiation for this (game, boards per tile, channels)");
+    return r;
+}
+
+extern "C" int azg_launch_support(int game, int channels) {
+    if (game < 0 || game >= k_num_games) return fail(AZG_E_INVALID_ARG, "unknown game id");
+    return tile_support(game, channels);
 }
 
 #ifdef AZG_TREE_TIMING

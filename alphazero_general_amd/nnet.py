@@ -407,12 +407,12 @@ class HipResNet:
 
     @property
     def can_search(self):
-        """a persistent search launch exists for this network: connect4 x 128 channels with fused heads (azg_search_f16), or
-        factorised heads on brandubh x 64 / the 3-player env x 32 / connect4 x {32, 64} / othello x {32, 64} channels -- the reference's
-        default net (Coach.py:108-116) is the 32-channel one -- (azg_search_wide_exact_f16 / azg_search_wide_f16); gobang x {32, 64, 128}
-        channels with exact heads only (azg_search_wide_exact_f16; 128 is the width of its own 128 x 8 training net, GOBANG_NET_ARGS)."""
-        return (self.fused_head and self.game == 0 and self.CH == 128) or (self.fact_head and (self.game, self.CH) in ((1, 64), (2, 32), (0, 32), (0, 64), (3, 32), (3, 64),
-                                                                                                                    (4, 32), (4, 64), (4, 128)))
+        """a persistent search launch exists for this network: fused heads (azg_search_f16) or factorised heads (azg_search_wide_exact_f16,
+        and azg_search_wide_f16 where the pair has sparse heads) on a (game, tower width) the library instantiates it for --
+        azg_launch_support answers from the library's own tile lists."""
+        from . import _abi
+        m = _abi.launch_support(self.game, self.CH)
+        return bool((self.fused_head and m & _abi.SUPPORT_SEARCH_FUSED) or (self.fact_head and m & _abi.SUPPORT_SEARCH_WIDE))
 
     @property
     def search_preferred(self):
@@ -517,7 +517,7 @@ class HipResNet:
 
     @staticmethod
     def search_arena_wide(nets, engine, sims, player_to_index=None, slot_seats=None):
-        """search_arena for factorised-head networks (azg_search_arena_wide_exact_f16: the pairs `can_search` lists, exact heads -- the
+        """search_arena for factorised-head networks (azg_search_arena_wide_exact_f16: the pairs with `can_search`, exact heads -- the
         bits NNetWrapper.process returns).  A None entry of `nets` is a raw seat: RawMCTSPlayer.process's constants (policy float32(1 / A),
         value zeros), no network runs for its games.  The real models must share (game, tower width, depth, feat_k)."""
         import ctypes as C
@@ -666,15 +666,17 @@ class NNetWrapper:
         return self.predict(board)
 
     def refresh(self):
-        """Rebuild the folded inference network after the weights changed."""
+        """Rebuild the folded inference network after the weights changed.  On a GPU, backend='auto' asks the library which (game,
+        tower width) pairs have an MFMA tower (azg_launch_support), so libazg_hip.so must be built -- an ImportError otherwise, as for
+        every other use of the GPU path; there is no quiet fall-back for a missing library."""
         net = FoldedResNet(self.nnet).to(self.device).to(self.dtype)
         if self.device.type == 'cuda':
             net = net.to(memory_format=torch.channels_last)
         self._infer, self._graph, self._hip = net.eval(), None, None
+        from . import _abi
         use_hip = self.backend == 'hip' or (self.backend == 'auto' and self.device.type == 'cuda'
-                                            and (getattr(self.game_cls, 'AZG_GAME_ID', None), self.args.num_channels) in
-                                            ((0, 32), (0, 64), (0, 128), (1, 64), (1, 128), (2, 32), (3, 32), (3, 64),
-                                             (4, 32), (4, 64), (4, 128)))
+                                            and _abi.launch_support(getattr(self.game_cls, 'AZG_GAME_ID', None), self.args.num_channels)
+                                            & _abi.SUPPORT_TOWER)
         if use_hip:
             self._hip = HipResNet(FoldedResNet(self.nnet).to(self.device), self.game_cls.AZG_GAME_ID, self.device)
         return self

@@ -381,6 +381,14 @@ int  azg_heads_softmax(void *stream, const float *logits_dev, int boards, int lo
  * padded width, lead rows, board stride}.  pixmap / qrow may be NULL.  AZG_E_UNSUPPORTED for a shape that is not instantiated. */
 int  azg_tower_layout(int game, int boards_per_tile, int channels, int16_t *pixmap, int32_t *qrow, int32_t *info8);
 
+/* Which network launches are instantiated for (game, tower width): a mask of AZG_SUPPORT_* bits, from the same tile lists the launches
+ * are built from (csrc/azg_tiles.h; no device needed).  AZG_E_INVALID_ARG for an unknown game. */
+int  azg_launch_support(int game, int channels);
+#define AZG_SUPPORT_TOWER         1   /* the stand-alone MFMA tower: azg_resnet_tower_f16 / azg_resnet_tower_features_f16              */
+#define AZG_SUPPORT_SEARCH_WIDE   2   /* factorised heads, exact: azg_search_wide_exact_f16 and azg_search_arena_wide_exact_f16        */
+#define AZG_SUPPORT_SEARCH_SPARSE 4   /* ... and the sparse-heads form of the self-play launch: azg_search_wide_f16                    */
+#define AZG_SUPPORT_SEARCH_FUSED  8   /* fused heads: azg_search_f16 / azg_search_arena_f16 (and azg_resnet_policy_value*_f16)         */
+
 /* ---- timing hooks for bench.py (HIP events on `stream` around the engine's own kernels) -------------------- */
 int  azg_profile_enable(azg_engine *e, int on);
 /* accumulated GPU ms + launch counts per kernel family: select, backup, advance. blocking. */

@@ -69,22 +69,15 @@ def test_no_cpu_fallback(built):
     assert b'no CPU fallback' in _abi.lib().azg_last_error()
 
 
-@pytest.mark.parametrize('game,bt,ch,H,W', [(0, 1, 128, 6, 7), (0, 2, 128, 6, 7), (0, 4, 128, 6, 7), (0, 4, 64, 6, 7),
-                                            (1, 1, 64, 7, 7), (1, 2, 64, 7, 7), (1, 2, 128, 7, 7), (2, 2, 32, 5, 5), (2, 5, 32, 5, 5)])
-def test_tower_lds_layout_invariants(game, bt, ch, H, W):
-    """The LDS image of the MFMA tower (csrc/azg_conv.h TowerGeom / tower_pixmap), checked on the host for every instantiated
-    shape: every pixel sits in exactly one (subtile, lane); all nine taps of a pixel are in-bounds rows; pad rows never
-    coincide with pixel rows; and the bank-conflict rule DESIGN.md states -- the 8 lanes {0-3,12-15} and the 8 lanes {4-11} of
-    a fragment read rows of pairwise different residue mod 8 (row stride = 2 (mod 4) 16-byte slots) -- holds wherever the
-    residue classes allow it (at most one doubled residue per 8-lane set)."""
-    import ctypes as C
+def check_tower_layout(L, game, bt, ch, H, W):
+    """the geometry-generic invariants of one tile's LDS image (azg_tower_layout): every pixel sits in exactly one (subtile, lane); all
+    nine taps of a pixel are in-bounds rows; inside taps hit the neighbour's row, pad rows never coincide with pixel rows; the row and
+    board strides keep the bank mapping DESIGN.md states.  Returns (nsub, rows, tile bytes, pixmap, qrow)."""
     import numpy as np
-    from alphazero_general_amd import _abi
-    L = _abi.lib()
     info = (C.c_int32 * 8)()
     assert L.azg_tower_layout(game, bt, ch, None, None, info) == 0
     nsub, rows, rstride, trows, tile, pw, lead, bstride = list(info)
-    assert rows == bt * H * W and nsub == (rows + 15) // 16 and tile == trows * rstride and tile <= 160 * 1024 // (2 if rows > 64 else 1)
+    assert rows == bt * H * W and nsub == (rows + 15) // 16 and tile == trows * rstride
     assert rstride == 2 * ch + 32 and (rstride // 16) % 4 == 2 and pw == W + 2 and bstride % 8 == 2
     pm = np.zeros(nsub * 16, np.int16); q = np.zeros(rows, np.int32)
     assert L.azg_tower_layout(game, bt, ch, pm.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), info) == 0
@@ -107,6 +100,24 @@ def test_tower_lds_layout_invariants(game, bt, ch, H, W):
                     assert r == q[b * H * W + (y + dy) * W + (x + dx)]
                 else:
                     assert r not in pixel_rows
+    return nsub, rows, tile, pm, q
+
+
+@pytest.mark.parametrize('game,bt,ch,H,W', [(0, 1, 128, 6, 7), (0, 2, 128, 6, 7), (0, 4, 128, 6, 7), (0, 4, 64, 6, 7),
+                                            (1, 1, 64, 7, 7), (1, 2, 64, 7, 7), (1, 2, 128, 7, 7), (2, 2, 32, 5, 5), (2, 5, 32, 5, 5)])
+def test_tower_lds_layout_invariants(game, bt, ch, H, W):
+    """The LDS image of the MFMA tower (csrc/azg_conv.h TowerGeom / tower_pixmap), checked on the host for the shapes of the
+    first three games' stand-alone towers (test_tower_layout_every_instantiated_shape: the generic part for every shape):
+    every pixel sits in exactly one (subtile, lane); all nine taps of a pixel are in-bounds rows; pad rows never
+    coincide with pixel rows; and the bank-conflict rule DESIGN.md states -- the 8 lanes {0-3,12-15} and the 8 lanes {4-11} of
+    a fragment read rows of pairwise different residue mod 8 (row stride = 2 (mod 4) 16-byte slots) -- holds wherever the
+    residue classes allow it (at most one doubled residue per 8-lane set)."""
+    import numpy as np
+    from alphazero_general_amd import _abi
+    L = _abi.lib()
+    info = (C.c_int32 * 8)()
+    nsub, rows, tile, pm, q = check_tower_layout(L, game, bt, ch, H, W)
+    assert tile <= 160 * 1024 // (2 if rows > 64 else 1)
     setA, setB = (0, 1, 2, 3, 12, 13, 14, 15), (4, 5, 6, 7, 8, 9, 10, 11)
     doubled = 0
     for s in range(nsub):
@@ -134,7 +145,45 @@ def test_tower_lds_layout_invariants(game, bt, ch, H, W):
             c = int(np.searchsorted(first, s, side='right') - 1)
             assert all(pclass(int(p)) == c for p in pm[s * 16:(s + 1) * 16] if p >= 0), (s, c)
         assert doubled == 0 or (bt, H, W) != (4, 6, 7)                       # the headline tile stays conflict-free
-    assert L.azg_tower_layout(game, 3, ch, None, None, info) == _abi.E_UNSUPPORTED
+    # a board count no tile of the pair has (brandubh x 64: its persistent launch has three- and four-game tiles)
+    assert L.azg_tower_layout(game, 5 if (game, ch) == (1, 64) else 3, ch, None, None, info) == _abi.E_UNSUPPORTED
+
+
+def test_tower_layout_every_instantiated_shape(built):
+    """azg_tower_layout answers for every (game, boards per tile, channels) a stand-alone tower or a persistent launch instantiates
+    (csrc/azg_tiles.h): the shapes are found by probing, not listed, and each one holds the generic invariants of the LDS image."""
+    from alphazero_general_amd import _abi
+    L = _abi.lib()
+    info = (C.c_int32 * 8)()
+    found = {(g, bt, ch) for g in range(5) for bt in range(1, 9) for ch in (32, 64, 128) if L.azg_tower_layout(g, bt, ch, None, None, info) == 0}
+    assert found >= {(0, 1, 128), (0, 2, 128), (0, 4, 128), (0, 4, 64), (0, 2, 32), (0, 4, 32), (1, 1, 64), (1, 2, 64), (1, 2, 128), (2, 2, 32), (2, 5, 32),
+                     (3, 1, 32), (3, 2, 32), (3, 4, 32), (3, 1, 64), (3, 2, 64), (3, 3, 64), (3, 4, 64), (4, 1, 32), (4, 1, 64), (4, 1, 128),
+                     (1, 3, 64), (1, 4, 64)}
+    assert (4, 2, 64) not in found and not any(L.azg_tower_layout(g, 1, 96, None, None, info) == 0 for g in range(5))
+    for g, bt, ch in sorted(found):
+        gi = _abi.game_info(g)
+        check_tower_layout(L, g, bt, ch, gi.obs_h, gi.obs_w)
+
+
+def test_launch_support_masks(built):
+    """azg_launch_support (derived from the tile lists of csrc/azg_tiles.h) against the pairs written out here -- the one place a
+    human-readable list remains; the tower bit agrees with what azg_tower_layout answers."""
+    from alphazero_general_amd import _abi
+    L = _abi.lib()
+    tower = {(0, 32), (0, 64), (0, 128), (1, 64), (1, 128), (2, 32), (3, 32), (3, 64), (4, 32), (4, 64), (4, 128)}
+    wide = {(1, 64), (2, 32), (0, 32), (0, 64), (3, 32), (3, 64), (4, 32), (4, 64), (4, 128)}
+    sparse = {p for p in wide if p[0] != 4}
+    fused = {(0, 128)}
+    info = (C.c_int32 * 8)()
+    for g in range(5):
+        for ch in (32, 64, 128):
+            want = (_abi.SUPPORT_TOWER * ((g, ch) in tower) | _abi.SUPPORT_SEARCH_WIDE * ((g, ch) in wide)
+                    | _abi.SUPPORT_SEARCH_SPARSE * ((g, ch) in sparse) | _abi.SUPPORT_SEARCH_FUSED * ((g, ch) in fused))
+            assert L.azg_launch_support(g, ch) == want == _abi.launch_support(g, ch), (g, ch)
+            assert ((g, ch) in tower) == any(L.azg_tower_layout(g, bt, ch, None, None, info) == 0 for bt in range(1, 9)), (g, ch)
+        assert L.azg_launch_support(g, 96) == 0
+    assert L.azg_launch_support(5, 64) < 0 and L.azg_launch_support(-1, 64) < 0
+    assert _abi.launch_support(None, 64) == 0 and _abi.launch_support(5, 64) == 0
 
 
 def test_source_stamp_covers_everything_the_binary_is_made_from(tmp_path, monkeypatch):
