@@ -15,6 +15,11 @@ range, and the reference's cast of the noise to float32 raises FloatingPointErro
 np.seterr(all='raise')) at the first noisy root.  gb_noise_tree.npz is the one noisy trace: make_goldens.gen_tree with root noise and
 temperature, run inside np.errstate(under='ignore') -- the reference's own arithmetic, with only the underflow trap turned off (the tiny
 draws become float32 denormals or zeros, as the cast rounds them).  There is no MT19937 whole-agent trace (that helper always adds noise).
+  gb_edge.npz           the tree edge family (make_goldens.gen_edge, asked for by name: `gb_edge`): roots of 225 down to 1 legal moves
+                        on both sides of every chunk of 64 children, 241 simulations each, and (under `rnd_`) four random prefixes of 1 to 29
+                        stones, 48 simulations each; per simulation a crc of the counts row, the
+                        full child arrays for the final tree.  Its noisy configs run, like gb_noise_tree, with only the underflow trap
+                        off, and the roots whose noise cast underflowed are counted apart (noise_cast_underflows)
 """
 import os
 import sys
@@ -243,6 +248,49 @@ AGENT_CONFIGS = [
 ]
 
 
+EDGE_KS = (193, 192, 191, 129, 128, 127, 66, 65, 64, 63, 2, 1)
+EDGE_FLOORS = dict(chosen_chunk1=100, chosen_chunk2=100, chosen_chunk3=100, tie_spans_chunks=500, nc_switch=50,
+                   zero_prior_selected_wide=20, seen_sum_serial_over128=50)
+
+
+def edge_roots(Game, seed, n_random=1, exact=True):
+    """reference games at the edge roots: random legal prefixes (the first one empty: 225 children), then one root per k of EDGE_KS
+    with exactly k = 225 - stones legal moves -- random legal playouts that reject a move completing a five, and for k = 2 and 1 a
+    full-board draw pattern of built_boards with two stones and one stone taken off"""
+    rng = np.random.RandomState(seed)
+    roots, kinds = [], []
+
+    def playout(n):
+        g = Game()
+        for a in rng.permutation(N * N):
+            if g.turns == n:
+                break
+            g2 = g.clone(); g2.play_action(int(a))
+            if not np.asarray(g2.win_state()).any():
+                g = g2
+        assert g.turns == n
+        return g
+    for r in range(n_random):
+        roots.append(playout(0 if r == 0 and exact else rng.randint(1, 30))); kinds.append(0)
+    if not exact:
+        return roots, kinds
+    full = next(b for kind, b in built_boards(np.random.RandomState(seed)) if kind == 'full' and (b != 0).all())
+    for k in EDGE_KS:
+        if k > 2:
+            g = playout(N * N - k)
+        else:
+            b = full.copy()
+            b.reshape(-1)[rng.choice(N * N, k, replace=False)] = 0
+            g = ref_from(Game, b.reshape(-1), (N * N - k) % 2, N * N - k)
+        roots.append(g); kinds.append(k)
+    return roots, kinds
+
+
+mg.EDGE_HOOKS['gb'] = dict(gid=GAME_GOBANG, sims=241, game_cls=ref_game, roots=edge_roots, cells=lambda g: pack(cells_of(g)),
+                           agent=(2, 8, 2), cov=mg.EDGE_COV_WIDE, floors=EDGE_FLOORS, compact=True,
+                           extra=dict(prefix='rnd_', sims=48, roots=lambda Game, seed: edge_roots(Game, seed, 4, exact=False)))
+
+
 def main(which=None, out_dir=HERE, verbose=True):
     which = which or ['gb_rules', 'gb_tree', 'gb_noise_tree', 'gb_agent']
     rh.import_reference()
@@ -257,6 +305,8 @@ def main(which=None, out_dir=HERE, verbose=True):
             mg.gen_tree(Game, GAME_GOBANG, 'gb_noise', n_roots=8, seed=43, configs=NOISE_CONFIGS, max_prefix=60)
     if 'gb_agent' in which:
         mg.gen_agent(Game, GAME_GOBANG, 'gb', configs=AGENT_CONFIGS, seed=717)
+    if 'gb_edge' in which:
+        mg.gen_edge('gb', out_dir=out_dir, verbose=verbose)
 
 
 if __name__ == '__main__':

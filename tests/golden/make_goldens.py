@@ -614,6 +614,20 @@ EDGE_COV = ['best_child_calls', 'tied_max', 'zero_prior_selected', 'seen_sum_tre
 EDGE_FLOORS = {                                            # per game, summed over the configs
     'tied_max': 500, 'zero_prior_selected': 50, 'seen_sum_tree': 100, 'seen_sum_serial_wide': 50, 'draw_backups': 100,
 }
+# The games without a C oracle (othello, gobang) register themselves here from their own generators (make_othello_goldens.py,
+# make_gobang_goldens.py: `ot_edge`, `gb_edge`): name -> dict(gid, sims, game_cls(), roots(game_cls, seed) -> (roots, kinds),
+# cells(g) -> the ABI cells of a reference game, agent (B, sims, games), cov [further counters], floors {counter: floor}, compact,
+# extra: a second group of roots dict(prefix, sims, roots) recorded the same way under `prefix` in the same file).  Their fixtures
+# carry the hook's `cov` counters (of EDGE_COV_WIDE) after those of EDGE_COV; the three oracle games' files are unchanged.
+EDGE_HOOKS = {}
+EDGE_COV_WIDE = [
+    'chosen_chunk1', 'chosen_chunk2', 'chosen_chunk3',     # the chosen child's list index is >= 64, >= 128, >= 192
+    'tie_spans_chunks',                                    # the maximal u are in at least two different chunks of 64 children
+    'nc_switch',                                           # one descent selects at a node of more than 64 children, then at one of at most 64
+    'zero_prior_selected_wide',                            # a zero-prior child chosen among more than 64
+    'seen_sum_serial_over128',                             # seen_sum_serial_wide at a node of more than 128 children
+    'noise_cast_underflows',                               # roots whose Dirichlet draw underflowed in the cast to float32 (MCTS.pyx:199-201)
+]
 
 
 def _edge_game_cls(name):
@@ -730,41 +744,86 @@ def _bc_observe(nd, chosen, cpuct, fpu, cov):
             cov['seen_sum_tree'] += 1
         else:
             cov['seen_sum_serial_wide'] += 1
+            if 'seen_sum_serial_over128' in cov:
+                cov['seen_sum_serial_over128'] += int(len(ch) > 128)
+    if 'chosen_chunk1' in cov:                              # (the games of EDGE_HOOKS: child lists of up to four chunks of 64)
+        for i in (1, 2, 3):
+            cov['chosen_chunk%d' % i] += int(best >= 64 * i)
+        cov['tie_spans_chunks'] += int(len(set((np.flatnonzero(u == u[best]) // 64).tolist())) > 1)
+        cov['zero_prior_selected_wide'] += int(chosen.p == 0 and len(ch) > 64)
 
 
-def gen_edge(name, seed=31, out_dir=None, verbose=True):
+def gen_edge(name, seed=31, out_dir=None, verbose=True, _group=None):
     import edge_eval as ee
     from alphazero.MCTS import MCTS
     out_dir = out_dir or OUT
-    gid, n_random, sims, ks = EDGE_GAMES[name]
-    game_cls = _edge_game_cls(name)
+    hook = EDGE_HOOKS.get(name)
+    if hook is None:
+        gid, n_random, sims, ks = EDGE_GAMES[name]
+        game_cls = _edge_game_cls(name)
+    else:
+        gid, sims, game_cls = hook['gid'], (_group or hook)['sims'], hook['game_cls']()
+    compact = bool(hook and hook['compact'])                # per simulation a crc of the counts row, not the root's n and q rows
+    cov_names = EDGE_COV + (hook['cov'] if hook else [])
     gi = ol.game_info(gid)
     A, NV, P = gi.action_size, gi.num_players + 1, gi.num_players
-    roots, kinds = _edge_roots(name, game_cls, gid, n_random, ks, seed)
+    if hook is None:
+        roots, kinds = _edge_roots(name, game_cls, gid, n_random, ks, seed)
+        ostates = [_root_state(name, gid, g) for g in roots]
+        cells = np.array([o.cells() for o in ostates], np.int8)
+        aux0 = [o.s.aux[0] for o in ostates]
+        root_k = [int(o.valid_moves().sum()) for o in ostates]
+    else:
+        roots, kinds = (_group or hook)['roots'](game_cls, seed)
+        cells = np.array([hook['cells'](g) for g in roots])
+        aux0 = [0] * len(roots)
+        root_k = [int(np.asarray(g.valid_moves()).sum()) for g in roots]
+        for g, kind, k in zip(roots, kinds, root_k):
+            assert not np.asarray(g.win_state()).any() and (kind == 0 or kind == k), (name, kind, k)
     R = len(roots)
-    ostates = [_root_state(name, gid, g) for g in roots]
-    out = dict(cells=np.array([o.cells() for o in ostates], np.int8), player=np.array([o.player for o in ostates], np.int32),
-               turns=np.array([o.turns for o in ostates], np.int32), aux0=np.array([o.s.aux[0] for o in ostates], np.int32),
+    out = dict(cells=cells, player=np.array([g.player for g in roots], np.int32),
+               turns=np.array([g.turns for g in roots], np.int32), aux0=np.array(aux0, np.int32),
                root_kind=np.array(kinds, np.int32), prob_temps=np.array(EDGE_PROB_TEMPS, np.float32), sims=np.int32(sims),
                configs=np.array([c[0] for c in EDGE_CONFIGS]))
-    KM = max(int(o.valid_moves().sum()) for o in ostates)
-    nunder = [0]
+    KM = max(root_k)
+    nunder, ncast, cast_pending = [0], [0], [False]
 
     def under(*_):
-        nunder[0] += 1
+        # cast_pending is set by the Dirichlet wrapper below only when the draw holds an entry whose cast to float32 traps (tiny and
+        # inexact).  _add_root_noise (MCTS.pyx:197-206) casts the draw at once and mixes it in with C floats, so the next trap IS that
+        # cast; any other trap of the same process_results call is booked as an ordinary underflow.
+        if cast_pending[0]:
+            ncast[0] += 1
+            cast_pending[0] = False
+        else:
+            nunder[0] += 1
     old_call = np.seterrcall(under)
     for (cname, fam, cpuct, fpu, nfrac, rtemp) in EDGE_CONFIGS:
-        cov = {k: 0 for k in EDGE_COV}
-        nunder[0] = 0
+        cov = {k: 0 for k in cov_names}
+        nunder[0] = ncast[0] = 0
         noise, temp = nfrac > 0, rtemp > 0
         tape = rh.Tape(seed * 1000 + rh.crc(np.frombuffer(cname.encode(), np.uint8)) % 997)
         tape.install()
+        if hook is not None:                                # (np.random.dirichlet is the tape's from here to uninstall)
+            taped = np.random.dirichlet
+
+            def dirichlet(alpha):
+                x = np.asarray(taped(alpha), np.float64)
+                with np.errstate(under='ignore'):
+                    y = x.astype(np.float32)
+                cast_pending[0] = bool(((np.abs(y) < np.finfo(np.float32).tiny) & (y.astype(np.float64) != x)).any())
+                return x
+            np.random.dirichlet = dirichlet
         try:
             args = rh.ref_args(game_cls, cpuct=cpuct, fpu_reduction=fpu, root_noise_frac=nfrac if noise else 0.1,
                                root_policy_temp=rtemp if temp else 1.1)
             paths = []
             depth = np.zeros((R, sims), np.int16)
-            rootn = np.zeros((R, sims, KM), np.int16); rootq = np.zeros((R, sims, KM), np.float32); rN = np.zeros((R, sims), np.int32)
+            rN = np.zeros((R, sims), np.int32)
+            if compact:
+                cnt_crc = np.zeros((R, sims), np.uint32)
+            else:
+                rootn = np.zeros((R, sims, KM), np.int16); rootq = np.zeros((R, sims, KM), np.float32)
             crcs = np.zeros((R, sims), np.uint32)
             fin = {k: [] for k in ('a', 'n', 'q', 'p', 'v', 'counts', 'probs', 'probs_raised', 'vmax', 'vavg', 'root_n', 'maxdepth', 'ctr')}
             for r in range(R):
@@ -776,6 +835,8 @@ def gen_edge(name, seed=31, out_dir=None, verbose=True):
                     pn = list(m._path)
                     for i, nd in enumerate(pn):
                         _bc_observe(nd, pn[i + 1] if i + 1 < len(pn) else m._curnode, cpuct, fpu, cov)
+                    if 'nc_switch' in cov and pn:           # (a child list only shrinks along a descent of these games)
+                        cov['nc_switch'] += int(len(pn[0]._children) > 64 and min(len(nd._children) for nd in pn) <= 64)
                     acts = [n.a for n in pn[1:]] + ([m._curnode.a] if pn else [])
                     depth[r, s] = m.depth
                     assert len(acts) == m.depth
@@ -789,8 +850,12 @@ def gen_edge(name, seed=31, out_dir=None, verbose=True):
                         cov['draw_backups'] += int(gv == np.float32(0.5))
                     with np.errstate(under='call'):                 # (the reference raises here)
                         m.process_results(leaf, v, p, noise, temp)
+                    cast_pending[0] = False
                     ch = m._root._children
-                    rootn[r, s, :len(ch)] = [c.n for c in ch]; rootq[r, s, :len(ch)] = [c.q for c in ch]
+                    if compact:
+                        cnt_crc[r, s] = rh.crc(np.asarray(m.counts(g)).astype(np.int32))
+                    else:
+                        rootn[r, s, :len(ch)] = [c.n for c in ch]; rootq[r, s, :len(ch)] = [c.q for c in ch]
                     rN[r, s] = m._root.n
                 ch = m._root._children
                 pad = KM - len(ch)
@@ -812,10 +877,15 @@ def gen_edge(name, seed=31, out_dir=None, verbose=True):
         finally:
             tape.uninstall()
         L = max(max(len(x) for x in paths), 1)
-        pa = np.full((R * sims, L), -1, np.int16)
+        pa = np.full((R * sims, L), 255, np.uint8) if compact else np.full((R * sims, L), -1, np.int16)   # (compact: actions < 255)
         for i, x in enumerate(paths):
             pa[i, :len(x)] = x
         cov['underflows'] = nunder[0]
+        assert noise or ncast[0] == 0, (name, cname)
+        if 'noise_cast_underflows' in cov:
+            cov['noise_cast_underflows'] = ncast[0]
+        else:
+            assert ncast[0] == 0, (name, cname)
         if fam != 'spread':
             assert nunder[0] == 0, (name, cname)                # only the spread rows underflow
         pre = cname + '_'
@@ -823,28 +893,50 @@ def gen_edge(name, seed=31, out_dir=None, verbose=True):
         out[pre + 'cfg'] = np.array([cpuct, fpu, nfrac, rtemp, sims], np.float64)
         out[pre + 'family'] = np.array(fam)
         out[pre + 'paths'] = pa.reshape(R, sims, L); out[pre + 'depth'] = depth
-        out[pre + 'rootn'] = rootn; out[pre + 'rootq'] = rootq; out[pre + 'rootN'] = rN; out[pre + 'row_crc'] = crcs
+        if compact:
+            out[pre + 'counts_crc'] = cnt_crc
+        else:
+            out[pre + 'rootn'] = rootn; out[pre + 'rootq'] = rootq
+        out[pre + 'rootN'] = rN; out[pre + 'row_crc'] = crcs
         for k, v in fin.items():
             out[pre + k] = np.array(v)
-        out[pre + 'cov'] = np.array([cov[k] for k in EDGE_COV], np.int64)
+        if compact:                                         # (narrow types: child actions as uint8 with 255 for -1; edge_eval.load undoes it)
+            assert A < 255 and int(depth.max()) < 256 and sims < 32768
+            out[pre + 'a'] = np.where(out[pre + 'a'] < 0, 255, out[pre + 'a']).astype(np.uint8)
+            out[pre + 'depth'] = depth.astype(np.uint8); out[pre + 'rootN'] = rN.astype(np.int16)
+        out[pre + 'cov'] = np.array([cov[k] for k in cov_names], np.int64)
         if verbose:
             print('  %s_edge/%s: max depth %d, %s' % (name, cname, int(depth.max()), cov))
     np.seterrcall(old_call)
-    out['cov_names'] = np.array(EDGE_COV)
+    out['cov_names'] = np.array(cov_names)
+    if _group is not None:                                  # a further group of roots: the caller stores it under its prefix
+        return ee.stack_configs(out), root_k
     tot = sum(out[c[0] + '_cov'] for c in EDGE_CONFIGS)
-    for k, floor in EDGE_FLOORS.items():
-        assert tot[EDGE_COV.index(k)] >= floor, (name, k, int(tot[EDGE_COV.index(k)]), floor)
+    for k, floor in dict(EDGE_FLOORS, **(hook['floors'] if hook else {})).items():
+        assert tot[cov_names.index(k)] >= floor, (name, k, int(tot[cov_names.index(k)]), floor)
     # the agent: uniform priors, draw-heavy values, temperature 0 from the first move (np.argmax ties in the counts), symmetric samples
-    o, _ = run_ref_agent(game_cls, gid, 'edge_agent', 6 if name != 'br' else 4, 12, 6 if name != 'br' else 3,
+    aB, asims, agames = hook['agent'] if hook else ((6, 12, 6) if name != 'br' else (4, 12, 3))
+    o, _ = run_ref_agent(game_cls, gid, 'edge_agent', aB, asims, agames,
                          dict(startTemp=0, temp_scaling_fn=_zero_temp), seed + 5, evaluator=ee.agent_row)
     for k, v in o.items():
         out['agent_' + k] = v
     out['agent_slot_base'] = np.int32(0)
+    if compact:                                             # the observations as bit planes + plane constants, checked to decode bit for bit
+        assert A < 255
+        out.update(ee.pack_obs(out.pop('agent_s_obs')))
+        out.update(ee.pack_pi(out.pop('agent_s_pi')))
+    extra_k, extra = [], {}
+    if hook and hook.get('extra'):
+        sub, extra_k = gen_edge(name, seed + 1, out_dir, verbose, _group=hook['extra'])
+        extra = {hook['extra']['prefix'] + k: v for k, v in sub.items()}
+    if compact:                                             # (one zip entry per key, not per key and config: an entry costs ~250 bytes)
+        out = ee.stack_configs(out)
+    out.update(extra)
     np.savez_compressed(os.path.join(out_dir, name + '_edge.npz'), **out)
     if verbose:
         print('%s_edge: %d roots (k = %s), %d configs; agent %d rounds, %d samples; coverage %s'
-              % (name, R, sorted(int(o.valid_moves().sum()) for o in ostates), len(EDGE_CONFIGS), len(o['actions']), len(o['s_pi']),
-                 dict(zip(EDGE_COV, tot.tolist()))))
+              % (name, R + len(extra_k), sorted(root_k) + sorted(extra_k), len(EDGE_CONFIGS), len(o['actions']), len(o['s_pi']),
+                 dict(zip(cov_names, tot.tolist()))))
 
 
 def _zero_temp(cur_temp, turns, const_max_turns):

@@ -7,6 +7,8 @@ Outputs (small .npz fixtures, committed):
   ot_tree.npz           single-tree MCTS traces (make_goldens.gen_tree): default, cpuct 4 / fpu 0.4, noise + temperature
   ot_agent.npz          SelfPlayAgent lock-step traces (make_goldens.gen_agent): plain, noisy, fastmix (symmetricSamples=False + probFastSim)
   ot_mt19937_agent.npz  a whole SelfPlayAgent under np.random.seed(s), every draw observed (make_goldens.gen_c4_mt19937_agent)
+  ot_edge.npz           the tree edge family (make_goldens.gen_edge, asked for by name: `ot_edge`): 12 random roots plus roots whose side
+                        to move has exactly one and exactly two legal moves
 The tree / agent helpers of make_goldens.py ask the oracle for the game's sizes (oracle_lib.game_info); the oracle has no othello, so
 this script answers that one call for game id 3 in-process and hands every other id through.
 """
@@ -115,6 +117,38 @@ AGENT_CONFIGS = [
 ]
 
 
+def edge_roots(Game, seed, n_random=12, ks=(1, 2)):
+    """reference games at the edge roots: random legal prefixes, then positions whose side to move has exactly k moves (the first
+    ones random playouts meet).  The reference's othello has no pass: a side without a move ends the game (othello.pyx:83-96), so
+    one legal move is the smallest root there is."""
+    rng = np.random.RandomState(seed)
+    roots, kinds = [], []
+    for r in range(n_random):
+        g = Game()
+        for _ in range(0 if r == 0 else rng.randint(0, 50)):
+            g2 = g.clone(); g2.play_action(int(rng.choice(np.flatnonzero(np.asarray(g.valid_moves())))))
+            if np.asarray(g2.win_state()).any():
+                break
+            g = g2
+        roots.append(g); kinds.append(0)
+    for k in ks:
+        found = None
+        while found is None:
+            g = Game()
+            while not np.asarray(g.win_state()).any():
+                v = np.flatnonzero(np.asarray(g.valid_moves()))
+                if len(v) == k:
+                    found = g
+                    break
+                g.play_action(int(rng.choice(v)))
+        roots.append(found); kinds.append(k)
+    return roots, kinds
+
+
+mg.EDGE_HOOKS['ot'] = dict(gid=GAME_OTHELLO, sims=60, game_cls=ref_game, roots=edge_roots, cells=cells_of, agent=(4, 12, 4),
+                           cov=[], floors={}, compact=False)
+
+
 def main(which=None, out_dir=HERE, verbose=True):
     which = which or ['ot_rules', 'ot_tree', 'ot_agent', 'ot_mt19937_agent']
     rh.import_reference()
@@ -128,6 +162,8 @@ def main(which=None, out_dir=HERE, verbose=True):
         mg.gen_agent(Game, GAME_OTHELLO, 'ot', configs=AGENT_CONFIGS, seed=515)
     if 'ot_mt19937_agent' in which:
         mg.gen_c4_mt19937_agent(B=4, sims=12, games=4, seed=20261015, eval_seed=97, Game=Game, gid=GAME_OTHELLO, name='ot')
+    if 'ot_edge' in which:
+        mg.gen_edge('ot', out_dir=out_dir, verbose=verbose)
 
 
 if __name__ == '__main__':

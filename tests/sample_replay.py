@@ -8,9 +8,9 @@ in order.  It never asks the engine, the C oracle or the device's symmetry table
 """
 import numpy as np
 
-from alphazero_general_amd.envs import brandubh, connect4, othello, trimok
+from alphazero_general_amd.envs import brandubh, connect4, gobang, othello, trimok
 
-GAMES = {0: connect4.Game, 1: brandubh.Game, 2: trimok.Game, 3: othello.Game}     # include/azg.h game ids
+GAMES = {0: connect4.Game, 1: brandubh.Game, 2: trimok.Game, 3: othello.Game, 4: gobang.Game}     # include/azg.h game ids
 
 
 def probs_t1(counts):

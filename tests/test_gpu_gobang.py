@@ -361,6 +361,79 @@ def test_gb_wide_search_deep_path():
     ea.close(); ec.close()
 
 
+def _flat_net(key, salt=7):
+    """the trained weights with the last Linear of both heads zeroed: every logit is 0, so every prior is the same after
+    masking and every value row is uniform -- PUCT ties at every node"""
+    args, sd, ref, x, o = _reference(key, salt=salt)
+    sd = {k: (torch.zeros_like(v) if k.rsplit('.', 1)[0] in ('pi_fc.4', 'v_fc.4') else v) for k, v in sd.items()}
+    assert sum(1 for k in sd if k.rsplit('.', 1)[0] in ('pi_fc.4', 'v_fc.4')) == 4
+    return _wrapper(args, sd)
+
+
+def _sparse_draw_states(ks, per_k, seed):
+    """per k, `per_k` positions with exactly k legal moves and no five: a full board of the two-on two-off draw pattern
+    (make_gobang_goldens.built_boards) with k random stones taken off -- taking stones off cannot make a five"""
+    Game = _game()
+    rng = np.random.RandomState(seed)
+    x, y = np.meshgrid(np.arange(15), np.arange(15), indexing='ij')
+    full = np.where((y // 2 + x) % 2 == 0, 1, -1).astype(np.int8).reshape(-1)
+    out = []
+    for k in ks:
+        for _ in range(per_k):
+            c = full.copy()
+            c[rng.choice(A, k, replace=False)] = 0
+            g = Game.from_azg_state(c, (A - k) % 2, A - k)
+            assert not g.win_state().any() and int(g.valid_moves().sum()) == k
+            out.append(g.to_azg_state())
+    return out
+
+
+def test_gb_wide_exact_search_at_exact_ties():
+    """the persistent launch (azg_search_wide_exact_f16) where every PUCT comparison ties: a flat network (all logits 0) on roots
+    of 225, 193, 129, 128, 66, 65, 64 and 30 legal moves -- first maxima out of ties that span chunks of 64 children, the switch
+    to the one-chunk templates inside a descent -- against the per-phase loop on a twin engine (which tests/test_gpu_tree_edges.py
+    holds to the reference at the same edges).  Root noise and temperature off."""
+    from alphazero_general_amd.engine import DeviceEngine
+    net = _flat_net('gobang_64x4')
+    ks, per_k, sims, moves = (225, 193, 129, 128, 66, 65, 64, 30), 6, 80, 2
+    B = len(ks) * per_k
+    assert B == 48
+    states = _sparse_draw_states(ks, per_k, 23)
+    kw = dict(cpuct=1.25, fpu_reduction=-1.0, seed=43, games_per_iteration=1 << 30, example_capacity=B * (moves + 1) * 8, sims_hint=sims)
+    ea, ec, ep = DeviceEngine(GB, B, **kw), DeviceEngine(GB, B, **kw), DeviceEngine(GB, B, **kw)
+    ea.set_states(states); ec.set_states(states); ep.set_states(states)
+    oc = ec.new_obs(torch.float32)
+    ep.select(oc)                                           # (a third engine: the twins' tapes stay in step)
+    p, v = net.process(oc)                                  # the network really ties: every row's entries are equal bit for bit
+    ep.close()
+    assert p.shape == (B, A) and v.shape == (B, NV)
+    assert bool((p == p[:, :1]).all()) and bool((v == v[:, :1]).all()) and bool((p > 0).all())
+    wide = 0
+    for mv in range(moves):
+        net._hip.search(ea, sims, exact=True)
+        for _ in range(sims):
+            ec.select(oc)
+            p, v = net.process(oc)
+            ec.backup(p.contiguous(), v.contiguous())
+        ca = ea.root_counts()
+        assert torch.equal(ca, ec.root_counts()), mv
+        assert torch.equal(ea.root_probs(1.0), ec.root_probs(1.0)) and torch.equal(ea.root_value(True), ec.root_value(True)), mv
+        assert torch.equal(ea.root_value(False), ec.root_value(False)), mv
+        assert mv > 0 or int(ca.sum()) == B * (sims - 1)         # (later moves search on in the kept subtree)
+        for i in range(B):                                  # visits landed on list indices past the first chunk
+            ch = ea.root_children(i)
+            wide += int((ch['n'][64:] > 0).sum())
+        ea.advance(True); ec.advance(True)
+        assert torch.equal(ea.last_actions(), ec.last_actions()), mv
+    assert wide > 0
+    assert (ea.tape_counters() == ec.tape_counters()).all()
+    assert ea.counters() == ec.counters()
+    for t, u in zip(ea.examples(), ec.examples()):
+        assert torch.equal(t, u)
+    assert all((a == b).all() for a, b in zip(ea.results(), ec.results()))
+    ea.close(); ec.close()
+
+
 # ------------------------------------------------------------------------------------------------------------------------- arena
 def _arena_nets(width, n, seed0=20):
     from alphazero_general_amd import nnet as N

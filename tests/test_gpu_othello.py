@@ -269,6 +269,50 @@ def test_ot_wide_exact_search_vs_phase_loop(key, B, sims, moves):
     ea.close(); ec.close()
 
 
+def test_ot_wide_exact_search_at_exact_ties():
+    """the persistent launch (azg_search_wide_exact_f16) where every PUCT comparison ties: a flat network -- the trained weights with
+    the last Linear of both heads zeroed, so every logit is 0, every prior the same after masking and every value row uniform -- on
+    the roots of tests/golden/ot_edge.npz (openings to late middle games, and the reference's smallest roots: one and two legal moves;
+    its othello has no pass action), four slots each, against the per-phase loop on a twin engine.  Root noise and temperature off."""
+    import edge_eval as ee
+    from alphazero_general_amd.engine import DeviceEngine
+    args, sd, ref, x, o = _reference('othello_64x4', salt=7)
+    last = ['%s.%d' % (h, max(int(k.split('.')[1]) for k in sd if k.startswith(h + '.'))) for h in ('pi_fc', 'v_fc')]
+    sd = {k: (torch.zeros_like(v) if k.rsplit('.', 1)[0] in last else v) for k, v in sd.items()}
+    assert sum(1 for k in sd if k.rsplit('.', 1)[0] in last) == 4 and sd[last[0] + '.weight'].shape[0] == 64
+    net = _wrapper(args, sd)
+    roots = ee.roots(dict(np.load(os.path.join(G, 'ot_edge.npz'))), OT)
+    ks = [int(g.valid_moves().sum()) for g in roots]
+    assert {1, 2} <= set(ks) and max(ks) >= 8
+    states = [g.to_azg_state() for g in roots] * 4
+    B, sims, moves = len(states), 60, 2
+    kw = dict(cpuct=1.25, fpu_reduction=-1.0, seed=47, games_per_iteration=1 << 30, example_capacity=B * (moves + 1) * 8, sims_hint=sims)
+    ea, ec, ep = DeviceEngine(OT, B, **kw), DeviceEngine(OT, B, **kw), DeviceEngine(OT, B, **kw)
+    ea.set_states(states); ec.set_states(states); ep.set_states(states)
+    oc = ec.new_obs(torch.float32)
+    ep.select(oc)                                           # (a third engine: the twins' tapes stay in step)
+    p, v = net.process(oc)                                  # the network really ties: every row's entries are equal bit for bit
+    ep.close()
+    assert p.shape == (B, 64) and bool((p == p[:, :1]).all()) and bool((v == v[:, :1]).all()) and bool((p > 0).all())
+    for mv in range(moves):
+        net._hip.search(ea, sims, exact=True)
+        for _ in range(sims):
+            ec.select(oc)
+            p, v = net.process(oc)
+            ec.backup(p.contiguous(), v.contiguous())
+        assert torch.equal(ea.root_counts(), ec.root_counts()), mv
+        assert torch.equal(ea.root_probs(1.0), ec.root_probs(1.0)) and torch.equal(ea.root_value(True), ec.root_value(True)), mv
+        assert torch.equal(ea.root_value(False), ec.root_value(False)), mv
+        ea.advance(True); ec.advance(True)
+        assert torch.equal(ea.last_actions(), ec.last_actions()), mv
+    assert (ea.tape_counters() == ec.tape_counters()).all()
+    assert ea.counters() == ec.counters()
+    for t, u in zip(ea.examples(), ec.examples()):
+        assert torch.equal(t, u)
+    assert all((a == b).all() for a, b in zip(ea.results(), ec.results()))
+    ea.close(); ec.close()
+
+
 @pytest.mark.parametrize('key', list(NETS))
 def test_ot_wide_sparse_search_vs_phase_loop(key):
     """azg_search_wide_f16 (sparse heads) against select -> tower features -> azg_leaf_heads_sparse_f16 -> softmax -> backup"""

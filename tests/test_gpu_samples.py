@@ -21,7 +21,9 @@ import sample_replay as sr
 pytestmark = pytest.mark.gpu
 
 SIMS, FAST_SIMS, PROB_FAST = 4, 2, 0.25
-SLOTS = {0: 64, 1: 32, 2: 96, 3: 32}                     # connect4, brandubh, the 3-player env, othello
+SLOTS = {0: 64, 1: 32, 2: 96, 3: 32, 4: 16}              # connect4, brandubh, the 3-player env, othello, gobang
+ROUNDS = {4: 340}                                        # gobang: this seeded run ends after 308 rounds; 3 * max_turns + 20 = 695 would size
+                                                         # example_capacity (rounds x slots x 8 symmetries, 4.5 KB a sample) at twice the need
 
 
 @pytest.fixture(scope='module')
@@ -101,7 +103,7 @@ def check(eng, rec, game, symmetric, cap=1 << 30, counted=None):
     return want
 
 
-@pytest.mark.parametrize('game', [0, 1, 2, 3])
+@pytest.mark.parametrize('game', [0, 1, 2, 3, 4])
 def test_samples_vs_host_replay(torch_mod, game):
     torch = torch_mod
     from alphazero_general_amd import _abi
@@ -109,7 +111,7 @@ def test_samples_vs_host_replay(torch_mod, game):
     t0 = time.time()
     gi = _abi.game_info(game)
     B, nsym = SLOTS[game], gi.num_symmetries
-    fast = np.random.RandomState(70 + game).random_sample(3 * gi.max_turns + 20) < PROB_FAST
+    fast = np.random.RandomState(70 + game).random_sample(ROUNDS.get(game, 3 * gi.max_turns + 20)) < PROB_FAST
     ex_cap = int((~fast).sum()) * B * nsym                   # every round adds at most B history entries
 
     def run(symmetric, cap=None, target=None):

@@ -1,9 +1,19 @@
 """The tree kernels (csrc/azg_kernels.h: best_child, leaf_policy / masked_sum, backup_path, root_probs, k_root_stats) held to the
-REFERENCE at its edges (pytest -m gpu): tests/golden/{c4,tm,br}_edge.npz, made by running the reference's MCTS.pyx /
+REFERENCE at its edges (pytest -m gpu): tests/golden/{c4,tm,br,ot,gb}_edge.npz, made by running the reference's MCTS.pyx /
 SelfPlayAgent.pyx on the tests/edge_eval.py rows -- exact PUCT ties, zero and denormal priors, both forms of the seen-policy
 sum, exact draw values, cpuct 0 / 50, fpu_reduction -1 / 0, noise_frac 1, root temperatures 0.5 / 2 / 1.1, roots with 1, 2,
 63, 64 and 65 children, paths of 24 and more actions.  The device is compared with the fixtures directly, not with the oracle
 (tests/test_oracle_golden.py pins the oracle to the same fixtures on the CPU).
+
+gb_edge is the four-chunk family (best_child<G, 4>, leaf_policy<G, 4>, the four-chunk add_children and the per-node switch to
+the one-chunk templates at k <= 64): roots of 225, 193, 192, 191, 129, 128, 127, 66, 65, 64, 63, 2 and 1 legal moves, 241
+simulations each (and, as `gbr`, four random prefixes of 201 to 220 legal moves, 48 simulations each), so that under the first-play bonus the first maximum sweeps every chunk out of ties that span chunks, zero
+priors are chosen among more than 64 children, the serial seen-sum runs over more than 128, and descents cross from wide
+nodes into k <= 64.  Its noisy configs hold the device to the reference's arithmetic with only numpy's underflow trap off
+(the float32 cast of a 225-way Dirichlet draw underflows).  ot_edge adds othello roots of one and two legal moves.  Both are
+replayed on the host envs (tests/test_edge_fixtures_cpu.py pins that replay, and checks every recorded action legal on the
+host rules; here the path is replayed only where the evaluator row depends on the leaf, the `onehot` family); gb_edge stores
+a crc of the counts row per simulation where the other fixtures store the root's n row.
 
 Every config runs on two engines fed the same rows: one per launch form, azg_select + azg_backup (one launch per phase) and
 azg_backup_select (k_backup_select2: backup k and select k + 1 in one launch, two wavefronts per tree).  Checked: every root's
@@ -16,16 +26,17 @@ np.seterr(all='raise')), the device returns the untrapped IEEE value of the same
 what is asserted.  The persistent search launches (azg_search_*) compute their own network, so they cannot take these injected
 rows; they reach the same select_tree / backup_path code and stay tied to it through the launch-equals-phase tests."""
 import os
+import zlib
 
 import numpy as np
 import pytest
 
 import edge_eval as ee
-import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-EDGE_CASES = [(n, c) for n in ('c4', 'tm', 'br') for c in ee.CONFIGS]
+NAMES = ('c4', 'tm', 'br', 'ot', 'gb')
+EDGE_CASES = [(n, c) for n in NAMES + ('gbr',) for c in ee.CONFIGS]      # gbr: the random-prefix roots gb_edge.npz holds under rnd_
 
 
 @pytest.fixture(scope='module')
@@ -36,10 +47,13 @@ def torch_mod():
 
 
 def _edge(name):
-    return dict(np.load(os.path.join(G, name + '_edge.npz')))
+    return ee.load(G, name)
 
 
 def _set_roots(eng, name, roots):
+    if ee.GAMES[name] in ee.HOST_GAMES:                      # host env games (gobang: 225 unpacked cells, engine.py packs them)
+        eng.set_states([g.to_azg_state() for g in roots])
+        return
     eng.set_states([(g.cells(), g.player, g.turns, g.s.aux[0]) if name == 'br' else (g.cells(), g.player, g.turns) for g in roots])
 
 
@@ -60,12 +74,12 @@ def test_edge_tree_vs_reference_goldens(torch_mod, name, cname):
     torch = torch_mod
     d = _edge(name)
     gid = ee.GAMES[name]
-    gi = ol.game_info(gid)
-    A, NV = gi.action_size, gi.num_players + 1
+    A, NV = ee.game_sizes(gid)
     cpuct, fpu, nfrac, rtemp, sims = d[cname + '_cfg']
     noise, temp, sims = bool(nfrac > 0), bool(rtemp > 0), int(sims)
     fam, seed = str(d[cname + '_family']), int(d[cname + '_seed'])
     exact = not temp or rtemp in (2.0, 0.5)
+    compact = cname + '_counts_crc' in d                     # (gb_edge: a crc of the counts row per simulation)
     roots = ee.roots(d, gid)
     R = len(roots)
     a_of = d[cname + '_a']                                   # root children in list order (fixed from the root's expansion on)
@@ -93,6 +107,12 @@ def test_edge_tree_vs_reference_goldens(torch_mod, name, cname):
                 engs[1].backup_select(tp, tv, None)
             else:
                 engs[1].backup(tp, tv)
+            if compact:
+                for e in engs:
+                    got = e.root_counts().cpu().numpy()
+                    assert got.dtype == np.int32 and got.shape == (R, A)
+                    assert [zlib.crc32(row.tobytes()) & 0xFFFFFFFF for row in got] == d[cname + '_counts_crc'][:, s].tolist(), s
+                continue
             want = np.zeros((R, A), np.int32)
             for r in range(R):
                 k = int((a_of[r] >= 0).sum())
@@ -129,11 +149,10 @@ def _zero_temp(cur_temp, turns, const_max_turns):
 
 
 @pytest.mark.parametrize('launch', ['phase', 'fused'])
-@pytest.mark.parametrize('name', ['c4', 'tm', 'br'])
+@pytest.mark.parametrize('name', NAMES)
 def test_edge_agent_vs_reference_goldens(torch_mod, name, launch):
     """SelfPlayAgent.run on the engine with the edge agent's rows (uniform priors, draw-heavy values) at temperature 0 from the
     first move, symmetric samples on: counts, moves, games, every sample and result as the reference made them"""
-    import zlib
     from alphazero_general_amd.engine import DeviceEngine
     torch = torch_mod
     d = _edge(name)
@@ -177,8 +196,9 @@ def test_edge_agent_vs_reference_goldens(torch_mod, name, launch):
         assert (np.array(rec['games_played']) == d['agent_games_played']).all()
         assert (np.array(rec['obs_crc'], np.uint32) == d['agent_obs_crc']).all()
         o, pi, z = [t.cpu().numpy() for t in eng.examples()]
-        assert o.shape == d['agent_s_obs'].shape
-        assert (o == d['agent_s_obs']).all() and (pi == d['agent_s_pi']).all() and (z == d['agent_s_z']).all()
+        want = ee.unpack_obs(d)
+        assert o.shape == want.shape
+        assert (o == want).all() and (pi == ee.unpack_pi(d)).all() and (z == d['agent_s_z']).all()
         ws, turns, slot = eng.results()
         assert (ws == d['agent_r_ws']).all() and (turns == d['agent_r_turns']).all()
     finally:

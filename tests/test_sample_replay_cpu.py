@@ -14,14 +14,15 @@ import pytest
 import sample_replay as sr
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-C4, BR, TM, OT = 0, 1, 2, 3
+C4, BR, TM, OT, GB = 0, 1, 2, 3, 4
 
 # (fixture, game, config, symmetricSamples): every config of the lock-step agent fixtures
 AGENT_FIXTURES = (
     [('c4_agent', C4, c, c != 'fastmix') for c in ('plain', 'noisy', 'fastmix', 'reset', 'warmup', 'config1')]
     + [('br_agent', BR, c, c != 'raw') for c in ('plain', 'noisy', 'wide', 'raw')]
     + [('tm_agent', TM, c, True) for c in ('plain', 'noisy', 'wide')]
-    + [('ot_agent', OT, c, c != 'fastmix') for c in ('plain', 'noisy', 'fastmix')])
+    + [('ot_agent', OT, c, c != 'fastmix') for c in ('plain', 'noisy', 'fastmix')]
+    + [('gb_agent', GB, c, c != 'fastmix') for c in ('plain', 'temp', 'fastmix')])
 MT_FIXTURES = [('c4_mt19937_agent', C4), ('br_mt19937_agent', BR), ('ot_mt19937_agent', OT)]
 
 _cache = {}
@@ -70,7 +71,7 @@ def test_raw_fixture_samples_positions_after_the_first_move():
 
 
 # ------------------------------------------------------------------------------------------------ the transforms themselves
-IDENTITY = {C4: 0, BR: 6, OT: 7}          # the entry of symmetries() that is (state, pi) itself
+IDENTITY = {C4: 0, BR: 6, OT: 7, GB: 7}          # the entry of symmetries() that is (state, pi) itself
 
 
 def positions(game, n, seed):
@@ -95,6 +96,9 @@ def test_identity_entries_are_what_the_reference_fixtures_imply():
     d = load('ot_rules')
     assert (d['sym_pi'][:, IDENTITY[OT]] == np.arange(64)).all()
     assert all((d['sym_pi'][:, k] != np.arange(64)).any(axis=1).all() for k in range(8) if k != IDENTITY[OT])
+    d = load('gb_rules')                                   # gobang: the same table (make_gobang_goldens gb_rules), 225 actions
+    assert (d['sym_pi'][:, IDENTITY[GB]] == np.arange(225)).all()
+    assert all((d['sym_pi'][:, k] != np.arange(225)).any(axis=1).all() for k in range(8) if k != IDENTITY[GB])
     # brandubh: br_rules.sym_crc row = [position, crc(cells_k) ^ crc(pi_k) for the reference's 8 entries, crc(pi)]
     d = load('br_rules')
     crc = lambda a: zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF  # noqa: E731
@@ -113,7 +117,7 @@ def test_identity_entries_are_what_the_reference_fixtures_imply():
     assert (s0.observation() == g.observation()).all() and (p0 == pi).all()
 
 
-@pytest.mark.parametrize('game,n', [(C4, 60), (BR, 12), (OT, 60)])
+@pytest.mark.parametrize('game,n', [(C4, 60), (BR, 12), (OT, 60), (GB, 60)])
 def test_replay_symmetries_identity_once_and_only_once(game, n):
     """on positions after the first move, the replay's symmetric block holds (state, pi) at IDENTITY[game] and every other
     entry differs from it in observation or pi; with symmetricSamples off the replay writes exactly (state, pi)"""
@@ -131,4 +135,4 @@ def test_replay_symmetries_identity_once_and_only_once(game, n):
             assert same == (k == IDENTITY[game]), k
         (s2, p2), = sr.samples_of(g, pi, False)
         assert (np.asarray(s2.observation()) == o).all() and (np.asarray(p2) == pi).all()
-    assert nsym == {C4: 2, BR: 8, OT: 8}[game]
+    assert nsym == {C4: 2, BR: 8, OT: 8, GB: 8}[game]
