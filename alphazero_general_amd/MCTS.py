@@ -5,7 +5,7 @@ that drives one tree at a time; the batched path (SelfPlayAgent) talks to a B-sl
 
 find_leaf / process_results are one kernel launch on a single wavefront plus a host sync each; `search(gs, nn, ...)` with this
 package's NNetWrapper runs all its simulations in ONE persistent launch (azg_search_f16 / azg_search_wide_f16) where the network has
-one.  The throughput path is `alphazero_general_amd.selfplay.SelfPlayRunner` / `SelfPlayAgent`.  Objects pickle (MCTS.pyx:8):
+one, and `raw_search(gs, sims, ...)` -- no network at all -- always does (azg_search_raw).  The throughput path is `alphazero_general_amd.selfplay.SelfPlayRunner` / `SelfPlayAgent`.  Objects pickle (MCTS.pyx:8):
 parameters, tape seed and a snapshot of the tree (azg_slot_export), so an MCTSPlayer can cross a process boundary.
 """
 import os
@@ -283,11 +283,28 @@ class MCTS:
             return self._via_ref(ref, 'raw_search', gs, sims, add_root_noise, add_root_temp)
         e = self._ensure(gs)
         e.reset_max_depth()
-        v = np.zeros(gs.num_players() + 1, dtype=np.float32)
-        p = np.full(gs.action_size(), 1, dtype=np.float32)
-        for _ in range(sims):
-            leaf = self.find_leaf(gs)
-            self.process_results(leaf, v, p, add_root_noise, add_root_temp)
+        if sims <= 0:
+            return
+        # all `sims` simulations -- find_leaf, the constant rows p = ones(A), v = zeros(P + 1) (:176-177), process_results -- in ONE
+        # launch (azg_search_raw) instead of two launches, two device-to-host reads and two host-to-device copies per simulation
+        # (GenericPlayers.RawMCTSPlayer.play calls this once per move).  Same trees as that loop, bit for bit; chunked to the node
+        # store exactly as search() above
+        v = np.zeros(e.NV, dtype=np.float32)
+        self._sync_root_state(gs)
+        e.set_search_flags(add_root_noise, add_root_temp)          # (per call; the engine's own defaults are restored below)
+        try:
+            left = int(sims)
+            while left > 0:
+                self._make_room(left * self._max_children)
+                fit = (e.nodes_per_tree - self._nodes_used) // self._max_children
+                n = min(left, fit) if fit >= 1 else left           # (not one expansion fits even after a compaction: let AZG_E_TREE_FULL surface)
+                e.search_raw(n, 1.0, v)
+                left -= n
+                info = e.tree_info(0)
+                self._nodes_used = info['nodes_used']
+        finally:
+            e.set_search_flags(False, False)                       # DeviceEngine's defaults for this class's one-slot engine (_ensure_game)
+        self.depth, self._max_depth = info['depth'], info['max_depth']
 
     def update_root(self, gs, a):                                      # MCTS.pyx:185-195 (raises ValueError)
         ref = self._fallback(gs)

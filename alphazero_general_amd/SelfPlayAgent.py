@@ -14,7 +14,10 @@ Where the search runs: Coach forks its agents AFTER initialising the GPU in the 
 use HIP.  The agent process therefore keeps the reference's role (queues, events, shared tensors) and drives a
 separate worker process (a fresh interpreter, alphazero_general_amd/_engine_worker.py) that owns the device engine; the two exchange the batch through POSIX shared memory
 and a pipe.  Compat mode pays that host hop per simulation by construction (the network lives in the parent); the
-throughput path is alphazero_general_amd.selfplay.SelfPlayRunner.  Errors in the worker are re-raised in the agent,
+throughput path is alphazero_general_amd.selfplay.SelfPlayRunner.  A warm-up agent (_is_warmup: the evaluation is a constant,
+:48-52) makes ONE worker call per round -- the worker runs the round's simulations in one launch, azg_search_raw -- so it looks
+at `stop_event` between rounds instead of between simulations; an interrupted round leaves nothing behind in the reference
+either (it breaks before playMoves); a warm-up agent in arena mode keeps the per-simulation calls (an arena engine has no such launch).  Errors in the worker are re-raised in the agent,
 which prints the traceback and exits like the reference (:100-101) -- but never leaves the parent waiting: it still
 counts itself complete.
 """
@@ -200,6 +203,13 @@ class SelfPlayAgent(mp.Process):
                 self._check_pause()
                 self.fast = np.random.random_sample() < a.probFastSim
                 sims = a.numFastSims if self.fast else a.numMCTSSims if not self._is_warmup else a.numWarmupSims
+                if self._is_warmup and not self._is_arena:          # (an arena engine has no such launch: its warm-up keeps the per-simulation calls below)
+                    # :48-52,111-114 the evaluation is a constant: the whole round -- sims x (find_leaf, uniform policy / value,
+                    # process_results) -- is ONE worker call and one launch (azg_search_raw) instead of two pipe round trips per
+                    # simulation.  stop_event is therefore honoured between rounds, not between simulations; nothing of an
+                    # interrupted round is observable in the reference either (it breaks before playMoves)
+                    self._call('search_raw', int(sims))
+                    sims = 0
                 for i in range(sims):
                     if self.stop_event.is_set(): break
                     self.generateBatch()
@@ -228,7 +238,7 @@ class SelfPlayAgent(mp.Process):
 
     def generateBatch(self):                                           # :103-135
         self._check_pause()
-        if self._is_warmup:
+        if self._is_warmup:                                            # (reached by a warm-up ARENA agent and by callers of this method; run() takes whole rounds)
             self._call('select_noobs')
             return
         if self._ahead is not None:                                    # (done together with the previous processBatch)

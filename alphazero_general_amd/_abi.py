@@ -96,6 +96,7 @@ SYMBOLS = {
     'azg_resnet_policy_value_f16': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     'azg_resnet_policy_value_multi_f16': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     'azg_search_f16': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i]),
+    'azg_search_raw': (_i, [_vp, _vp, _f, _f32p, _i]),
     'azg_policy_value_heads_f16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'azg_tower_layout': (_i, [_i, _i, _i, _vp, _vp, _vp]),
     'azg_launch_support': (_i, [_i, _i]),

@@ -61,6 +61,9 @@ def engine_worker(conn, cfg):
             elif cmd == 'select_noobs':
                 eng.select(None)
                 conn.send(('ok', None))
+            elif cmd == 'search_raw':                            # a warm-up agent's whole round (arg simulations) in one launch:
+                eng.search_raw(int(arg), np.float32(1.0 / cfg['A']), np.full(cfg['NV'], 1.0 / cfg['NV'], np.float32))   # SelfPlayAgent.pyx:48-52
+                conn.send(('ok', None))
             elif cmd == 'backup':
                 pv_in()
                 if pinned:

@@ -322,6 +322,20 @@ extern "C" int azg_backup(azg_engine *e, void *stream, const float *policy, cons
     return AZG_OK;
 }
 
+extern "C" int azg_search_raw(azg_engine *e, void *stream, float policy_fill, const float *value_host, int sims) {
+    if (!e || !value_host || sims < 0) return fail(AZG_E_INVALID_ARG, "null or out-of-range argument");
+    if (e->v.arena) return fail(AZG_E_UNSUPPORTED, "the network-free search launch is built for self-play engines (one tree per slot)");
+    if (sims == 0) return AZG_OK;
+    hipStream_t s = (hipStream_t)stream;
+    GAME_SWITCH(e, {
+        RawValueRow<G> vrow;                                    // both constant rows go by value: nothing of the caller's is read after the call
+        for (int j = 0; j < G::P + 1; j++) vrow.v[j] = value_host[j];
+        hipLaunchKernelGGL((k_search_raw<G>), dim3(e->v.B), dim3(64), 0, s, e->v, policy_fill, vrow, sims);
+    });
+    HIPCHK(hipGetLastError());
+    return AZG_OK;
+}
+
 extern "C" int azg_backup_select(azg_engine *e, void *stream, const float *policy, const float *value, const int32_t *row_of_slot, int flags,
                                  void *obs, int obs_dtype) {
     if (!e || !policy || !value) return fail(AZG_E_INVALID_ARG, "null argument");

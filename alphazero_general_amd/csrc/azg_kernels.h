@@ -561,6 +561,74 @@ __global__ __launch_bounds__(64) void k_backup(View ev, const float *policy, con
     backup_slot<G>(ev, slot, threadIdx.x, policy + (size_t)row * G::A, value + (size_t)row * (G::P + 1), m_lds, scr);
 }
 
+// ================================================================================================ network-free search
+// `sims` whole simulations of a slot WITHOUT a network in one launch -- MCTS.raw_search (MCTS.pyx:175-183), a warm-up agent's round
+// (SelfPlayAgent.pyx:48-52,87-92,111-114): per simulation the code of k_select with no observation sink, then the code of k_backup fed
+// a policy row of A copies of `policy_fill` and the value row `vrow`.  The reference refills p and v every simulation (`pi *= valids`
+// rebinds, it never writes the caller's buffer), so every leaf sees the pristine constant row: it is written to LDS once.  Both rows
+// travel in the kernel arguments (a captured graph replays without reading host memory).
+// The slot's header, last path, tape counter, tallies and root state live in LDS for the length of the launch (the View's pointers
+// are offset so that [tree] / [slot] lands on the mirror, as the persistent wide-head launch does): what one simulation writes
+// there the next one reads without an L2 round trip; node blocks and the leaf state stay in HBM.  One wavefront per tree: no waits.
+// The wavefront stops simulating after the simulation in which its OWN tree raised a sticky error -- a full node store (the
+// expansion came back without a child block) or a constant row that cannot be normalised (policy_fill <= 0: leaf_policy raised
+// AZG_E_FLOATING_POINT) -- which is where the launch-per-phase form stops as well, and every 16th simulation when any tree has.
+template <class G> struct RawValueRow { float v[G::P + 1]; };
+template <class G>
+__global__ __launch_bounds__(64) void k_search_raw(View ev, float policy_fill, RawValueRow<G> vrow, int sims) {
+    if (__builtin_amdgcn_readfirstlane(ev.gcount[GC_ERROR]) != 0) return;   // sticky device error: stop touching the trees
+    constexpr int A = G::A, MAXD = G::MAX_TURNS + 2;
+    __shared__ int act_lds[((G::MAXK + 63) / 64) * 64];
+    __shared__ float m_lds[A < 8 ? 8 : A];
+    __shared__ float scr[64];
+    __shared__ float pi_lds[A];
+    __shared__ __attribute__((aligned(64))) TreeHdr hdr_lds;
+    __shared__ __attribute__((aligned(16))) PathEnt path_lds[MAXD];
+    __shared__ __attribute__((aligned(16))) azg_state state_lds;
+    __shared__ __attribute__((aligned(8))) uint64_t ctr_lds[3];              // tape counter, slot_sims, slot_exp
+    static_assert(sizeof(TreeHdr) == 4 * sizeof(uint4) && sizeof(azg_state) % 16 == 0 && sizeof(PathEnt) == sizeof(uint4),
+                  "the LDS mirror moves the header, the root state and the path as whole 16-byte chunks");
+    const int slot = blockIdx.x, tree = slot, lane = threadIdx.x;           // (self-play engines only: one tree per slot)
+    if (ev.maxd > MAXD) { if (lane == 0) raise_error(ev, AZG_E_INTERNAL); return; }      // (the path mirror holds the game's longest path)
+    for (int a = lane; a < A; a += 64) pi_lds[a] = policy_fill;
+    if (lane < 4) reinterpret_cast<uint4 *>(&hdr_lds)[lane] = reinterpret_cast<const uint4 *>(ev.hdr + tree)[lane];
+    if (lane < (int)sizeof(azg_state) / 16) reinterpret_cast<uint4 *>(&state_lds)[lane] = reinterpret_cast<const uint4 *>(ev.states + slot)[lane];
+    if (lane == 0) { ctr_lds[0] = ev.tape_ctr[slot]; ctr_lds[1] = (uint64_t)ev.slot_sims[slot]; ctr_lds[2] = (uint64_t)ev.slot_exp[slot]; }
+    View evl = ev;
+    evl.hdr = &hdr_lds - tree;
+    evl.path = path_lds - (size_t)tree * ev.maxd;
+    evl.states = &state_lds - slot;
+    evl.tape_ctr = ctr_lds - slot;
+    evl.slot_sims = reinterpret_cast<int64_t *>(ctr_lds + 1) - slot;
+    evl.slot_exp = reinterpret_cast<int64_t *>(ctr_lds + 2) - slot;
+    wave_sync();
+    for (int sim = 0; sim < sims; sim++) {
+        if (sim > 0 && (sim & 15) == 0 && __hip_atomic_load(&ev.gcount[GC_ERROR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
+        // (an opaque copy of the lane id, new in every simulation: nothing a phase derives from it is invariant in the loop, so the
+        //  per-lane constants of find_leaf and of process_results are not hoisted out of it and kept live through each other.  The
+        //  mask gives the copy back its range: the tree functions are shared with every other tree launch, and what the compiler
+        //  knows about THEIR `lane` argument is the union over all callers)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        ln &= 63;
+        select_slot<G>(evl, slot, ln, act_lds, [](const typename G::S &, int) {});
+        wave_sync();
+        asm volatile("" : "+v"(ln));
+        ln &= 63;
+        backup_slot<G>(evl, slot, ln, pi_lds, vrow.v, m_lds, scr);
+        wave_sync();
+        const bool no_block = hdr_lds.leaf_fc < 0;                           // (find_leaf raised: the store is full, or a replayed tape ran out)
+        const bool terminal = ((hdr_lds.leaf_info >> 16) & 0xFFu) != 0;      // (a terminal leaf takes no policy: nothing to normalise)
+        if (no_block || (!terminal && !(policy_fill > 0.f))) break;
+    }
+    wave_sync();
+    if (lane < 4) reinterpret_cast<uint4 *>(ev.hdr + tree)[lane] = reinterpret_cast<const uint4 *>(&hdr_lds)[lane];
+    const int depth = hdr_lds.depth;
+    for (int j = lane; j < depth && j < ev.maxd; j += 64)
+        reinterpret_cast<uint4 *>(ev.path + (size_t)tree * ev.maxd)[j] = reinterpret_cast<const uint4 *>(path_lds)[j];
+    if (lane == 0) { ev.tape_ctr[slot] = ctr_lds[0]; ev.slot_sims[slot] = (int64_t)ctr_lds[1]; ev.slot_exp[slot] = (int64_t)ctr_lds[2]; }
+}
+
 // hand-off flags between the two wavefronts of a slot (LDS, workgroup-scope release / acquire).
 // Generation flags: the producer stores `gen`, the consumer waits for a value >= gen.  Every wait is BOUNDED (~10^7 polls, seconds):
 // a hand-off that never comes -- it cannot, both wavefronts run the same uniform control flow -- must not hang the GPU; it raises

@@ -244,6 +244,19 @@ class DeviceEngine:
         _abi.check(self.L.azg_heads_softmax(_stream(), _ptr(logits), int(logits.shape[0]), int(logits.shape[1]), self.A, self.NV, _ptr(pol), _ptr(val)))
         return pol, val
 
+    def search_raw(self, sims, policy_fill, value_row):
+        """`sims` whole simulations without a network on every slot in ONE launch (azg_search_raw): find_leaf, then process_results fed
+        a policy row of float32(policy_fill) in every entry and the value row value_row[P + 1]; the engine's root flags
+        (set_search_flags).  MCTS.raw_search's rows are (1.0, zeros), a warm-up agent's (1 / A, full(1 / NV)).  Both rows are copied at the
+        call.  Same trees as `sims` x [select(None), backup(those rows)]."""
+        v = None
+        if value_row is not None:
+            v = np.ascontiguousarray(np.asarray(value_row, np.float32).reshape(-1))
+            if v.size != self.NV:
+                raise ValueError('value_row must hold P + 1 = %d entries' % self.NV)
+            v = v.ctypes.data_as(C.POINTER(C.c_float))
+        _abi.check(self.L.azg_search_raw(self.h, _stream(), float(np.float32(policy_fill)), v, int(sims)))
+
     def advance(self, record_history=True):
         _abi.check(self.L.azg_advance(self.h, _stream(), int(bool(record_history))))
 

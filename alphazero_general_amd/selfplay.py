@@ -7,13 +7,14 @@ communication during search; finished examples are all-gathered once per iterati
 """
 import time
 
+import numpy as np
 import torch
 
 from . import _abi
 from .engine import DeviceEngine
 from .nnet import HipResNet
 from .Game import azg_game_id
-from .utils import AGENT_STREAM, default_temp_scaling
+from .utils import AGENT_STREAM, default_temp_scaling, raw_launch_default
 
 
 # The persistent launch of a wide-head network hands the tree NNetWrapper.process's own bits by default ('exact': visit counts and pi
@@ -41,7 +42,10 @@ class SelfPlayRunner:
     def __init__(self, game_cls, nnet, args, *, num_slots, seed=0, slot_base=0, device=None, example_capacity=None,
                  use_graph=True, obs_dtype=torch.float16, warmup=False, pipelines=1, round_graph=None, result_capacity=None,
                  fused_search=None, heads=None, nodes_per_tree=0, search_heads=None):
-        """heads: what the tree launch is fed when the search is launched per phase -- None follows search_heads ('exact', the default:
+        """fused_search: the whole simulation loop of a move as ONE persistent launch -- True insists on it, False keeps the launch-per-phase
+        loop, None takes the faster form: for a network HipResNet.search_preferred, for warm-up (no network: azg_search_raw, the constant
+        rows in the launch's arguments) utils.raw_launch_default('warmup').
+        heads: what the tree launch is fed when the search is launched per phase -- None follows search_heads ('exact', the default:
         'logits' for wide heads -- all A + P+1 logits, softmax inside the tree launch --, else 'probs'; 'sparse': 'features' for
         factorised heads -- the launch computes the logits of the valid actions itself); tests pin each form against the oracle.
         search_heads: the same choice for the persistent launch of a factorised-heads network.  nodes_per_tree: node store of a tree
@@ -116,6 +120,17 @@ class SelfPlayRunner:
         hip = getattr(nnet, '_hip', None) if nnet is not None else None
         self.fused_search = (hip.search_preferred if fused_search is None and hip is not None else bool(fused_search)) and self.round_graph \
             and not self.warmup and hip is not None and hip.can_search and self.game == hip.game
+        if self.warmup:                                              # ... or the network-free launch: needs no graph, no network
+            self.fused_search = self.warmup_raw_round(fused_search)
+            # SelfPlayAgent.pyx:48-52 in the launch's arguments: float32(1 / A) in every policy entry, float32(1 / NV) in every value
+            # entry -- the bits of the constant tensors above
+            self._raw_fill = float(np.float32(1 / self.engine.A))
+            self._raw_value = np.full(self.engine.NV, 1 / self.engine.NV, np.float32)
+
+    @staticmethod
+    def warmup_raw_round(fused_search):
+        """does a warm-up runner created with this `fused_search` run its rounds as one azg_search_raw launch + advance?"""
+        return raw_launch_default('warmup') if fused_search is None else bool(fused_search)
 
     @property
     def obs(self):
@@ -157,7 +172,10 @@ class SelfPlayRunner:
         backup k and select k + 1 sharing a launch (or the whole loop in one persistent launch)."""
         e = ln.engine
         if self.fused_search:
-            self.nnet._hip.search(e, sims, exact=self.search_exact)
+            if self.warmup:
+                e.search_raw(sims, self._raw_fill, self._raw_value)
+            else:
+                self.nnet._hip.search(e, sims, exact=self.search_exact)
             e.advance(record_history=not fast)
             return
         e.select(ln.obs)
@@ -191,7 +209,7 @@ class SelfPlayRunner:
         key = (sims, fast)
         if key not in ln.round_graphs:
             e = ln.engine
-            if self.fused_search:
+            if self.fused_search and not self.warmup:
                 self.nnet._hip.search(e, 0, exact=self.search_exact)  # one-time setup outside the capture
             torch.cuda.synchronize(e.device)
             g = torch.cuda.CUDAGraph()
@@ -216,11 +234,13 @@ class SelfPlayRunner:
     def play_round(self, eager=False):
         """eager=True issues the captured launch sequence as plain launches (measurement: events between the launches)."""
         sims, fast = self._sims_for_round()
-        if self.round_graph and eager:
+        profiling = any(getattr(ln.engine, 'profiling', False) for ln in self.lanes)
+        raw = self.warmup and self.fused_search                      # (one launch + advance: issued as it is where no graph replays it)
+        if (self.round_graph and eager) or (raw and (eager or profiling or not self.round_graph)):
             for ln in self.lanes:
                 with torch.cuda.stream(ln.stream), torch.no_grad():
                     self._issue_round(ln, sims, fast)
-        elif self.round_graph and not any(getattr(ln.engine, 'profiling', False) for ln in self.lanes):
+        elif self.round_graph and not profiling:
             for ln in self.lanes:
                 with torch.cuda.stream(ln.stream):
                     self._round_graph(ln, sims, fast).replay()

@@ -46,3 +46,20 @@ def temp_table(temp_fn, start_temp, max_turns):
 
 
 AGENT_STREAM = 0x4000000000000000   # tape stream of agent-level draws (fast coin, seat shuffle); DESIGN.md
+
+
+# Searches that use no network -- MCTS.raw_search (RawMCTSPlayer) and the rounds of a warm-up agent -- can run their whole simulation
+# loop as ONE launch (azg_search_raw).  A caller takes that form BY DEFAULT only where tools/raw_search_throughput.py measured it faster
+# than the launch-per-phase form of the commit before it by more than the spread of the repeats, at EVERY (game, slots) size listed for
+# that caller; otherwise it stays opt-in (SelfPlayRunner(fused_search=True)).  The numbers: profiles/raw_search_throughput.json,
+# DESIGN.md "Network-free searches in one launch".
+RAW_LAUNCH = {
+    # (MCTS.raw_search has no other form left: the entry records that the rule was met, and at which sizes)
+    'raw_search': dict(default=True, sizes=[('connect4', 1), ('brandubh', 1)]),                         # ms per MCTS.raw_search(g, 100) move
+    'warmup': dict(default=False, sizes=[(g, b) for g in ('connect4', 'brandubh') for b in (128, 512, 2048)]),   # ms per round, numWarmupSims = 5
+}
+
+
+def raw_launch_default(caller):
+    """does `caller` ('raw_search' or 'warmup') run its network-free simulations as one azg_search_raw launch unless told otherwise?"""
+    return bool(RAW_LAUNCH[caller]['default'])

@@ -323,6 +323,18 @@ int  azg_search_wide_exact_f16(azg_engine *e, void *stream, const void *w_packed
                                const float *head1_b_dev, const void *wps_packed_dev, const void *wv_packed_dev, const float *head_b_dev,
                                int feat_k, int sims);
 
+/* `sims` whole simulations without a network -- MCTS.raw_search (MCTS.pyx:175-183), a warm-up agent's round
+ * (SelfPlayAgent.pyx:48-52,87-92,111-114) -- on every slot of a self-play engine in ONE launch: find_leaf, then process_results
+ * fed a policy row of `policy_fill` in every one of the A entries and the value row value_host[P+1]; engine root flags
+ * (azg_set_root_flags) as the other persistent launches.  Results identical to `sims` x [azg_select(obs = NULL), azg_backup with
+ * those rows] -- every tree, counter, leaf state and the last path as azg_last_path reads it; the path buffer's entries BEYOND the last
+ * simulation's depth, which nothing reads, are not written (the per-phase form leaves older, deeper paths there: the dead bytes of an
+ * azg_slot_export taken afterwards may differ).  Every game with device rules; one wavefront per slot, the slot's header, path and tape counter stay in LDS between
+ * the simulations.  Both rows are copied at the call (a captured graph replays without reading value_host).  sims == 0: nothing is
+ * launched.  A tree whose node store fills up stops expanding and leaves the sticky AZG_E_TREE_FULL; policy_fill <= 0 leaves the
+ * sticky AZG_E_FLOATING_POINT (a policy whose valid entries sum to 0).  AZG_E_UNSUPPORTED: an arena engine. */
+int  azg_search_raw(azg_engine *e, void *stream, float policy_fill, const float *value_host, int sims);
+
 /* Bounds-checked builds (alphazero_general_amd/build.py --variant debug, -DAZG_DEBUG_BOUNDS; the reference compiles its own checks out,
  * MCTS.pyx:2-6): every node / child-block / path index of the tree kernels is checked before use; a violation raises the sticky
  * AZG_E_INTERNAL and is skipped.  *site = the first check that failed (0: none), *checked = 1 if this binary carries the checks. */
