@@ -112,7 +112,13 @@ class GameState:
         raise NotImplementedError('Symmetries not implemented for this environment. Set symmetricSamples to False in args.')
 
 
+# (the reference's own tictactoe class is NOT listed: behind install() it keeps going to the reference's classes, the fall-through env
+#  that tests/test_install_conformance.py pins; the device game is this package's envs.tictactoe.Game)
 _REFERENCE_ENVS = {'envs.connect4.connect4': 0, 'envs.brandubh.fastafl': 1, 'envs.othello.othello': 3, 'envs.gobang.gobang': 4}
+# device games whose class reports max_turns() None (the reference's default, Game.py:56-58): scale_temp never steps for them
+# (utils.py:19-23).  The value is the longest game: what azg_game_info.max_turns sizes history and paths with, and the number of turns a
+# temperature table has to cover -- never the schedule's max_turns argument.
+UNBOUNDED_TURNS = {5: 9}
 
 
 def azg_game_id(game_cls_or_state):
@@ -136,6 +142,17 @@ def azg_game_id(game_cls_or_state):
             err = NotImplementedError('%s, and the hand-over to the reference\'s own alphazero.%s failed: %s: %s' % (msg, name, type(ex).__name__, ex))
             raise err from ex
     raise NotImplementedError(msg)
+
+
+def schedule_turns(game_cls_or_state):
+    """turns a temperature table of this game has to cover: the class's max_turns(), or the longest game where that is None"""
+    mt = game_cls_or_state.max_turns() if hasattr(game_cls_or_state, 'max_turns') else None
+    if mt:
+        return mt
+    try:
+        return UNBOUNDED_TURNS.get(azg_game_id(game_cls_or_state))
+    except NotImplementedError:
+        return None
 
 
 def has_device_rules(game_cls_or_state):

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 import torch.multiprocessing as mp
 
-from .Game import azg_game_id, has_device_rules
+from .Game import azg_game_id, has_device_rules, schedule_turns
 from .utils import default_temp_scaling, temp_table
 
 
@@ -101,7 +101,8 @@ class SelfPlayAgent(mp.Process):
         self._pol_h = np.ndarray((B, A), np.float32, buffer=self._shm['pol'].buf)
         self._val_h = np.ndarray((B, NV), np.float32, buffer=self._shm['val'].buf)
         sims = max(int(a.get('numMCTSSims', 100) or 0), int(a.get('numFastSims', 0) or 0), int(a.get('numWarmupSims', 0) or 0))
-        tt = temp_table(a.get('temp_scaling_fn', default_temp_scaling), a.get('startTemp', 1.0), self.game_cls.max_turns())
+        tt = temp_table(a.get('temp_scaling_fn', default_temp_scaling), a.get('startTemp', 1.0), self.game_cls.max_turns(),
+                        schedule_turns(self.game_cls))
         seed = int(a.get('_azg_seed', int.from_bytes(os.urandom(7), 'little'))) + 7919 * int(self.id)    # :81 np.random.seed()
         cfg = dict(game=gid, B=B, A=A, NV=NV, O=O, arena=bool(self._is_arena), temp_table=tt,
                    player_to_index=list(getattr(self, 'player_to_index', [])),

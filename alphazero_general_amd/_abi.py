@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('AZG_LIB_PATH') or os.path.join(HERE, 'lib', 'libazg_hip.so')   # (override: measurement builds)
 ABI_VERSION = 7
 
-GAME_CONNECT4, GAME_BRANDUBH, GAME_TRIMOK, GAME_OTHELLO, GAME_GOBANG = 0, 1, 2, 3, 4
+GAME_CONNECT4, GAME_BRANDUBH, GAME_TRIMOK, GAME_OTHELLO, GAME_GOBANG, GAME_TICTACTOE = 0, 1, 2, 3, 4, 5
 E_INVALID_ARG, E_HIP, E_INVALID_ACTION, E_TREE_FULL, E_EXAMPLES_FULL, E_UNSUPPORTED, E_INTERNAL, E_FLOATING_POINT = -1, -2, -3, -4, -5, -6, -7, -8
 SUPPORT_TOWER, SUPPORT_SEARCH_WIDE, SUPPORT_SEARCH_SPARSE, SUPPORT_SEARCH_FUSED = 1, 2, 4, 8      # azg_launch_support
 ERROR_NAMES = {-1: 'AZG_E_INVALID_ARG', -2: 'AZG_E_HIP', -3: 'AZG_E_INVALID_ACTION', -4: 'AZG_E_TREE_FULL',

@@ -133,6 +133,20 @@ static bool tower_pixmap(int16_t *map /*[NSUB*16]*/) {          // false: a clas
             const int *lanes = (k & 1) ? setB : setA; int ps = s0 + (k >> 1), li = 0;
             for (int r = 0; r < 8; r++) if (used[r] < cnt[r] && used[r] <= k) map[ps * 16 + lanes[li++]] = (int16_t)cls[r][used[r]++];
         }
+        // a board smaller than one subtile (3x3: PW = 5, BSTRIDE = 26) can leave a class only FOUR residues -- the interior pixel of board b
+        // sits at 2 b + const -- so half of such a class is leftovers: they go to the free lanes one residue after the other, which gives
+        // an 8-lane set every residue twice (a two-way conflict) where filling residue by residue would put three lanes on one
+        if (GEO::HW < 16) {
+            int r = 0;
+            for (int i = s0 * 16; i < s1 * 16; i++) {
+                if (map[i] >= 0) continue;
+                int tries = 0;
+                while (tries < 8 && used[r] >= cnt[r]) { r = (r + 1) & 7; tries++; }
+                if (tries == 8) break;
+                map[i] = (int16_t)cls[r][used[r]++];
+                r = (r + 1) & 7;
+            }
+        }
         for (int r = 0; r < 8; r++)
             while (used[r] < cnt[r]) {
                 bool placed = false;

@@ -51,8 +51,9 @@ static const azg_game_info k_info[] = {
     {TM::A, TM::OBS_C, TM::H, TM::W, TM::P, TM::HAS_DRAW, TM::MAX_TURNS, TM::NSYM, TM::CELLS, TM::MAXK},
     {OT::A, OT::OBS_C, OT::H, OT::W, OT::P, OT::HAS_DRAW, OT::MAX_TURNS, OT::NSYM, OT::CELLS, OT::MAXK},
     {GB::A, GB::OBS_C, GB::H, GB::W, GB::P, GB::HAS_DRAW, GB::MAX_TURNS, GB::NSYM, GB::CELLS, GB::MAXK},
+    {TT::A, TT::OBS_C, TT::H, TT::W, TT::P, TT::HAS_DRAW, TT::MAX_TURNS, TT::NSYM, TT::CELLS, TT::MAXK},
 };
-static const int k_num_games = 5;
+static const int k_num_games = 6;
 
 extern "C" int azg_abi_version(void) { return AZG_ABI_VERSION; }
 #ifndef AZG_SRC_SHA
@@ -99,9 +100,11 @@ template <typename T> static int dalloc(azg_engine *e, T **p, size_t count) {
     case AZG_GAME_TRIMOK: { using G = TM; CALL; } break; \
     case AZG_GAME_OTHELLO: { using G = OT; CALL; } break; \
     case AZG_GAME_GOBANG: { using G = GB; CALL; } break; \
+    case AZG_GAME_TICTACTOE: { using G = TT; CALL; } break; \
     default: return fail(AZG_E_UNSUPPORTED, "game has no device rules"); }
 // the same for the sparse heads (head features -> logits of the leaf's children only): not built for gobang, where nearly every
-// cell is a legal move, so a sparse row saves little and the 3616-wide feature dot products would spill
+// cell is a legal move, so a sparse row saves little and the 3616-wide feature dot products would spill, nor for tic-tac-toe, whose
+// nine logits are one output subtile either way
 #define SPARSE_GAME_SWITCH(e, CALL) \
     switch ((e)->cfg.game) { \
     case AZG_GAME_CONNECT4: { using G = C4; CALL; } break; \
@@ -109,6 +112,7 @@ template <typename T> static int dalloc(azg_engine *e, T **p, size_t count) {
     case AZG_GAME_TRIMOK: { using G = TM; CALL; } break; \
     case AZG_GAME_OTHELLO: { using G = OT; CALL; } break; \
     case AZG_GAME_GOBANG: return fail(AZG_E_UNSUPPORTED, "no sparse heads for gobang (use the dense heads)"); \
+    case AZG_GAME_TICTACTOE: return fail(AZG_E_UNSUPPORTED, "no sparse heads for tic-tac-toe (use the dense heads)"); \
     default: return fail(AZG_E_UNSUPPORTED, "game has no device rules"); }
 // dispatch on the observation format the tree kernels write (obs_dtype 0: f32 planes, 1: f16 planes, 2: f16 NHWC8 rows): CALL sees the
 // element type OBS, the flag NHWC8 and the buffer as OBS *o
@@ -1031,6 +1035,12 @@ static int dispatch_tower(hipStream_t s, int game, int channels, const TowerPara
         if (bt == 1) ks = 2; else { bt = 2; if (sp == 2) ps = 2; }
     } else if (game == AZG_GAME_GOBANG) {                            // one board per tile, three pixel groups, at every width
         bt = 1; ps = 3;
+    } else if (game == AZG_GAME_TICTACTOE && channels == 32) {
+        // one wavefront per workgroup in every shape: one board (one subtile, 7 spare lanes) while that fills no more than 8 wavefronts per
+        // CU, five boards (three subtiles, three border classes) up to 16 workgroups per CU, then sixteen (nine full subtiles, five border
+        // classes: 57 of 81 subtile-taps).  The thresholds are the occupancy argument alone: nothing for this game has been measured
+        bt = forced ? forced : n <= 8 * cus ? 1 : n <= 80 * cus ? 5 : 16;
+        if (bt != 1 && bt != 5) bt = 16;
     }
     return tower_tile_launch(s, game, channels, bt, ps, ks, P);
 }
@@ -1355,6 +1365,7 @@ static int search_wide(azg_engine *e, void *stream, const void *w, const float *
     if (wide_max_tile(e->cfg.game, channels) == 0)
         return fail(AZG_E_UNSUPPORTED, "persistent wide-head search: built for the pairs azg_launch_support gives AZG_SUPPORT_SEARCH_WIDE (use azg_select / network / azg_backup)");
     if (!EXACT && e->cfg.game == AZG_GAME_GOBANG) return fail(AZG_E_UNSUPPORTED, "no sparse heads for gobang (use the exact persistent launch)");
+    if (!EXACT && e->cfg.game == AZG_GAME_TICTACTOE) return fail(AZG_E_UNSUPPORTED, "no sparse heads for tic-tac-toe (use the exact persistent launch)");
     TowerParams P = tower_params(nullptr, w, bias, pre_scale, pre_shift, e->v.B, nblocks);
     set_fact_heads(P, head1_w, head1_b, nullptr, feat_k); P.A = A; P.NV = NV;
     hipStream_t s = (hipStream_t)stream;
@@ -1529,6 +1540,8 @@ extern "C" int azg_tower_layout(int game, int boards_per_tile, int channels, int
 
 extern "C" int azg_launch_support(int game, int channels) {
     if (game < 0 || game >= k_num_games) return fail(AZG_E_INVALID_ARG, "unknown game id");
+    // tic-tac-toe is built for 32-channel towers only (both of its nets): any other width is refused, not answered with an empty mask
+    if (game == AZG_GAME_TICTACTOE && channels != 32) return fail(AZG_E_UNSUPPORTED, "tic-tac-toe has 32-channel launches only");
     return tile_support(game, channels);
 }
 

@@ -720,4 +720,98 @@ struct GB {
     }
 };
 
+
+// ================================================================================================ tictactoe
+// alphazero/envs/tictactoe/tictactoe.py + TicTacToeLogic.py: 3x3, three in a row.  Cell i = 3x + y of the reference's pieces[x][y] (action a
+// places a stone on cell a, every empty cell is legal -- also at a position that is already won), colour 1 for player 0 and -1 for
+// player 1.  One 9-bit bitboard per colour in SGPRs.  The reference's max_turns() is None (Game.py:56-58: turns never decide anything and
+// the temperature schedule never steps, utils.py:19-23); MAX_TURNS = 9 here only sizes history, paths and the default node store.
+struct TT {
+    static constexpr int ID = AZG_GAME_TICTACTOE;
+    static constexpr int A = 9, H = 3, W = 3, CELLS = 9, P = 2, HAS_DRAW = 1, MAX_TURNS = 9, NSYM = 8;
+    static constexpr int OBS_C = 1, OBS = OBS_C * CELLS, MAXK = 9;
+    static constexpr int SYM_RAW = 7;                                    // the identity is the LAST entry of symmetries(), as othello
+    static constexpr uint32_t FULL = 0x1FFu;
+    struct S { uint32_t b0, b1; int player, turns; };                    // b0: colour 1 (player 0), b1: colour -1
+
+    static AZG_DEV S load(const azg_state *st, int lane) {
+        const int8_t v = lane < CELLS ? st->cells[lane] : (int8_t)0;
+        S s;
+        s.b0 = (uint32_t)__ballot(v == 1);
+        s.b1 = (uint32_t)__ballot(v == -1);
+        s.player = __builtin_amdgcn_readfirstlane(st->player);
+        s.turns = __builtin_amdgcn_readfirstlane(st->turns);
+        return s;
+    }
+    static AZG_DEV void init(S &s) { s.b0 = s.b1 = 0; s.player = 0; s.turns = 0; }
+    static AZG_DEV int cell(const S &s, int i) { return (int)((s.b0 >> i) & 1) - (int)((s.b1 >> i) & 1); }
+    static AZG_DEV void store(const S &s, azg_state *st, int lane) {
+        st->cells[lane] = lane < CELLS ? (int8_t)cell(s, lane) : (int8_t)0;
+        if (lane == 0) { st->player = s.player; st->turns = s.turns; st->aux[0] = 0; st->aux[1] = 0; }
+    }
+    static AZG_DEV uint64_t valid_mask(const S &s) { return ~(s.b0 | s.b1) & FULL; }            // get_legal_moves (TicTacToeLogic.py:39-52)
+    static AZG_DEV void play(S &s, int a) {                              // execute_move (TicTacToeLogic.py:107-116) + Game.py:76-79
+        const uint32_t bit = 1u << (__builtin_amdgcn_readfirstlane(a) & 15);
+        if (s.player == 0) s.b0 |= bit; else s.b1 |= bit;
+        s.player ^= 1; s.turns += 1;
+    }
+    // is_win (TicTacToeLogic.py:61-105): the counts along a strip are never reset, so on a 3-wide board a strip wins iff all three of
+    // its cells hold the colour: the three y-strips (bits y, 3 + y, 6 + y), the three x-strips, the two diagonals
+    static AZG_DEV bool has3(uint32_t m) {
+        return (m & 0x049u) == 0x049u || (m & 0x092u) == 0x092u || (m & 0x124u) == 0x124u ||
+               (m & 0x007u) == 0x007u || (m & 0x038u) == 0x038u || (m & 0x1C0u) == 0x1C0u ||
+               (m & 0x111u) == 0x111u || (m & 0x054u) == 0x054u;
+    }
+    // win_state (tictactoe.py:67-78): the mover's line first, then the opponent's, then a draw if no cell is empty -- on a built board
+    // where both colours hold a line the player to move wins
+    static AZG_DEV int win_bits(const S &s) {
+        const uint32_t own = s.player == 0 ? s.b0 : s.b1, opp = s.player == 0 ? s.b1 : s.b0;
+        if (has3(own)) return 1 << s.player;
+        if (has3(opp)) return 1 << (s.player ^ 1);
+        return (s.b0 | s.b1) == FULL ? 4 : 0;
+    }
+    // lane i < k receives the i-th empty cell in ascending order (A = 9: unrolled select, as connect4)
+    static AZG_DEV int valid_list(const S &s, int lane, int *act_lds, int (&my_a)[1]) {
+        const uint32_t vm = (uint32_t)valid_mask(s);
+        const int k = __popc(vm);
+        int a = -1, cnt = 0;
+#pragma unroll
+        for (int c = 0; c < A; c++) { if ((vm >> c) & 1) { if (cnt == lane) a = c; cnt++; } }
+        my_a[0] = a; (void)act_lds;
+        return k;
+    }
+    // observation (tictactoe.py:80-81): one plane of the raw pieces, absolute colours
+    template <typename OT_> static AZG_DEV void write_obs(const S &s, OT_ *out, int lane) { if (lane < CELLS) out[lane] = (OT_)(float)cell(s, lane); }
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    static AZG_DEV h8 obs8(const S &s, int lane) {
+        return (h8){(_Float16)(float)cell(s, lane), (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+    }
+    static AZG_DEV void write_obs_nhwc8(const S &s, _Float16 *out, int lane) {
+        if (lane < CELLS) *reinterpret_cast<h8 *>(out + lane * 8) = obs8(s, lane);
+    }
+    // symmetries (tictactoe.py:83-102): entry k = 2(i-1) + (0 if flipped else 1), i = 1..4: fliplr^flip(rot90^i(pieces)), so k = 7 is the
+    // identity.  np.rot90: out[r][c] = in[c][2-r]; np.fliplr: out[r][c] = in[r][2-c]
+    static AZG_DEV S symmetry(const S &s, int k) {
+        const int lane = threadIdx.x & 63;
+        const int i = k / 2 + 1;
+        const int l9 = lane < CELLS ? lane : 0;
+        int r = l9 / 3, c = l9 - (l9 / 3) * 3;
+        if ((k & 1) == 0) c = 2 - c;
+        for (int t = 0; t < i; t++) { const int nr = c, nc = 2 - r; r = nr; c = nc; }
+        const int src = r * 3 + c;
+        S o = s;
+        o.b0 = (uint32_t)__ballot(lane < CELLS && ((s.b0 >> src) & 1));
+        o.b1 = (uint32_t)__ballot(lane < CELLS && ((s.b1 >> src) & 1));
+        return o;
+    }
+    // where pi[a] lands under symmetry k (the forward maps: rot90 sends (r, c) to (2-c, r), fliplr (r, c) to (r, 2-c))
+    static AZG_DEV int sym_action(int a, int k) {
+        const int i = k / 2 + 1;
+        int r = a / 3, c = a - (a / 3) * 3;
+        for (int t = 0; t < i; t++) { const int nr = 2 - c, nc = r; r = nr; c = nc; }
+        if ((k & 1) == 0) c = 2 - c;
+        return r * 3 + c;
+    }
+};
+
 }  // namespace azg

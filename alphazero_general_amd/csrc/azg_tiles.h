@@ -49,6 +49,12 @@ namespace azg {
     X(GB,  32, 1, 3, 1) \
     X(GB,  64, 1, 3, 1) \
     X(GB, 128, 1, 3, 1) \
+    /* tic-tac-toe: a 3x3 board is 9 pixels, less than one pixel subtile.  One wavefront per workgroup in every shape: one board (one */ \
+    /* subtile, 7 spare lanes), five boards (45 pixels: three subtiles, one per border class of the three-class form), sixteen boards */ \
+    /* (144 pixels: exactly nine subtiles and no spare lane; the five-class form, 1 interior + 3 + 3 row + 1 + 1 column subtiles) */ \
+    X(TT,  32, 1, 1, 1) \
+    X(TT,  32, 5, 1, 1) \
+    X(TT,  32, 16, 1, 1) \
     AZG_TOWER_TILES_TUNING(X)
 
 // ---- persistent wide-search tiles (azg_search_wide_f16, azg_search_wide_exact_f16): X(game, channels, games per workgroup, PSPLIT, MINB,
@@ -82,11 +88,17 @@ namespace azg {
     /* twelve wavefronts, one workgroup per CU, the streamed heads loop (heads_full_stream) */ \
     X(GB,  32, 1, 3, 1, 1) \
     X(GB,  64, 1, 3, 1, 1) \
-    X(GB, 128, 1, 3, 1, 1)
+    X(GB, 128, 1, 3, 1, 1) \
+    /* tic-tac-toe x 32 (envs/tictactoe/train.py's 32 x 4 net and the default net): connect4-32's shapes.  The board is ONE pixel subtile, */ \
+    /* so the second pixel group of the one-game tile (the helper's wavefront) and groups 2, 3 of the two-game tile own no subtile: they */ \
+    /* run the layers on the zero pad row and store nothing (k_tower2: gs < NSUBT); exact heads only (has_sparse_heads) */ \
+    X(TT,  32, 1, 2, 1, 1) \
+    X(TT,  32, 2, 4, 2, 1)   /* walker + helper per game */
 
 // sparse heads (head features -> logits of the leaf's children only) are not built for gobang, where nearly every cell is a legal
 // move: a sparse row saves little and the 3616-wide feature dot products would spill
-template <class G> constexpr bool has_sparse_heads = G::ID != AZG_GAME_GOBANG;
+// nor for tic-tac-toe: A = 9 is one output subtile, which the exact heads compute whole at the same cost
+template <class G> constexpr bool has_sparse_heads = G::ID != AZG_GAME_GOBANG && G::ID != AZG_GAME_TICTACTOE;
 
 // azg_launch_support: the AZG_SUPPORT_* mask of (game, tower width); 0 for a game id the lists do not know
 inline int tile_support(int game, int channels) {

@@ -37,8 +37,11 @@ class DeviceEngine:
         self.A, self.NV, self.P = gi.action_size, gi.num_players + 1, gi.num_players
         self.obs_shape = (gi.obs_c, gi.obs_h, gi.obs_w)
         self.O = gi.obs_c * gi.obs_h * gi.obs_w
+        # (the schedule follows the game's class: azg_game_info.max_turns is a sizing number, and for a game whose class has no turn
+        #  limit -- tic-tac-toe -- the reference's scale_temp never steps)
+        from .Game import UNBOUNDED_TURNS
         self._tt = (np.ascontiguousarray(temp_table_override, np.float32) if temp_table_override is not None
-                    else temp_table(temp_fn, start_temp, gi.max_turns))
+                    else temp_table(temp_fn, start_temp, None if game in UNBOUNDED_TURNS else gi.max_turns, gi.max_turns))
         cfg = _abi.Config()
         # nodes_per_tree = 0: the library sizes the two node semi-spaces of a tree from sims_per_move (every simulation expands
         # at most one node = max_children stubs; dead siblings are reclaimed by compaction after a move)

@@ -25,6 +25,7 @@ import torch
 import torch.distributed as dist
 
 from . import distributed as D
+from .Game import schedule_turns
 from .utils import dotdict, default_temp_scaling, temp_table
 
 
@@ -299,7 +300,7 @@ def portable_args(args, game_cls):
     """the picklable slice of a Coach's args; the temperature schedule (a callable, utils.py:19-31) travels as its table"""
     out = {k: args[k] for k in ARG_KEYS if k in args}
     out['_azg_temp_table'] = temp_table(args.get('temp_scaling_fn', default_temp_scaling), args.get('startTemp', 1.0),
-                                        game_cls.max_turns()).tolist()
+                                        game_cls.max_turns(), schedule_turns(game_cls)).tolist()
     return out
 
 

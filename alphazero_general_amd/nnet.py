@@ -22,6 +22,8 @@ OTHELLO_NET_ARGS = dotdict(num_channels=64, depth=4, value_head_channels=16, pol
                            value_dense_layers=[512, 256], policy_dense_layers=[512])             # envs/othello/train.py:25-30
 GOBANG_NET_ARGS = dotdict(num_channels=128, depth=8, value_head_channels=16, policy_head_channels=16,
                           value_dense_layers=[2048, 128], policy_dense_layers=[2048])           # envs/gobang/train.py:37-43
+TICTACTOE_NET_ARGS = dotdict(num_channels=32, depth=4, value_head_channels=4, policy_head_channels=4,
+                             value_dense_layers=[128, 64], policy_dense_layers=[128])           # envs/tictactoe/train.py:24-29
 
 
 def _mlp(sizes):
@@ -300,20 +302,25 @@ class HipResNet:
             # the heads FACTORISED like the reference computes them (1x1 head convs in the tower launch, then the collapsed
             # Linear chains on 16 + 16 head channels per pixel): a quarter of the collapsed matrix's weight traffic at 64 channels
             pc = hw.shape[0] - vc
-            self.fact_head = (not self.fused_head) and vc == 16 and pc == 16
+            # (fewer than 16 head channels -- envs/tictactoe/train.py's 4 + 4 -- take the same path zero-padded to 16 + 16: zero rows and
+            #  biases in the 1x1 head convolution make the padded features exact zeros, and the chain matrices keep zero rows at their slots;
+            #  16 + 16 packs byte for byte as without the padding)
+            self.fact_head = (not self.fused_head) and 1 <= vc <= 16 and 1 <= pc <= 16
             if self.fact_head:
                 FK = (HW * 16 + 31) // 32 * 32
                 self.feat_k = FK
-                w1 = torch.cat([hw[vc:], hw[:vc]])                                            # [32, CH]: policy rows, then value rows
+                pad16 = lambda t: torch.cat([t, t.new_zeros((16 - t.shape[0],) + tuple(t.shape[1:]))])
+                w1 = torch.cat([pad16(hw[vc:]), pad16(hw[:vc])])                              # [32, CH]: policy rows, then value rows
                 # A fragments [ks][ms][lane g*16+i][j] = W1[ms*16 + i, ks*32 + g*8 + j]
                 self.head1_w = w1.reshape(2, 16, CH // 32, 4, 8).permute(2, 0, 3, 1, 4).contiguous().reshape(-1) \
                                  .to(self.device, torch.float16).contiguous()
-                self.head1_b = torch.cat([hb[vc:], hb[:vc]]).to(**f32).contiguous()
+                self.head1_b = torch.cat([pad16(hb[vc:]), pad16(hb[:vc])]).to(**f32).contiguous()
                 OSP = (A + 15) // 16
                 w2p = torch.zeros((FK, OSP * 16), dtype=torch.float32, device=Wp.device)      # feature pos*16 + c  <-  flatten index c*HW + pos
-                w2p[:HW * 16, :A] = Wp.reshape(A, pc, HW).permute(2, 1, 0).reshape(HW * pc, A)
+                pad_c = lambda t, c: torch.cat([t, t.new_zeros((HW, 16 - c, t.shape[2]))], 1).reshape(HW * 16, -1)   # [HW, c, out] -> [HW * 16, out]
+                w2p[:HW * 16, :A] = pad_c(Wp.reshape(A, pc, HW).permute(2, 1, 0), pc)
                 w2v = torch.zeros((FK, 16), dtype=torch.float32, device=Wv.device)
-                w2v[:HW * 16, :NV] = Wv.reshape(NV, vc, HW).permute(2, 1, 0).reshape(HW * vc, NV)
+                w2v[:HW * 16, :NV] = pad_c(Wv.reshape(NV, vc, HW).permute(2, 1, 0), vc)
                 frag = lambda w, osub: w.reshape(FK // 32, 4, 8, osub, 16).permute(0, 3, 1, 4, 2).contiguous().reshape(-1) \
                                         .to(self.device, torch.float16).contiguous()
                 self.head2_wp, self.head2_wv = frag(w2p, OSP), frag(w2v, 1)
@@ -421,7 +428,8 @@ class HipResNet:
         launch-per-phase loop at 128-2048 games (profiles/gobang_throughput.json).  Gobang x 128 (streamed heads, 672 B/lane): its A/B
         against the per-phase loop (tools/gobang_throughput.py --nets gobang_128x8) has NOT been measured yet, so the flag stays false --
         it turns true only on a measurement that shows the persistent form faster at 128, 512 and 2048 games by more than the spread
-        (DESIGN.md 7c); fused_search=True takes the launch meanwhile."""
+        (DESIGN.md 7c); fused_search=True takes the launch meanwhile.  Tic-tac-toe x 32 met that rule (profiles/tictactoe_throughput.json, both
+        nets: 13.1 / 47.3 / 62.8 M simulations/s against 2.6 / 10.5 / 41.6 at 128 / 512 / 2048 games, spreads below 1.7 M), so it is true there."""
         return self.can_search and self.game != 4
 
     def search(self, engine, sims, exact=False):

@@ -34,12 +34,14 @@ def const_temp_scaling(temp, *args, **kwargs):
     return temp
 
 
-def temp_table(temp_fn, start_temp, max_turns):
+def temp_table(temp_fn, start_temp, max_turns, turns=None):
     """temp_by_turn[t]: the temperature SelfPlayAgent.playMoves uses for the move made at turn t, i.e.
     args.temp_scaling_fn iterated from args.startTemp (alphazero/SelfPlayAgent.pyx:156-157).  The callable is
-    evaluated on the host once; the device indexes the table."""
+    evaluated on the host once; the device indexes the table.  `max_turns` is what the game's CLASS reports and the
+    callable receives -- None for a game without a turn limit, where the default schedule never steps; `turns`
+    (default: max_turns) is how many turns the table covers."""
     out, t = [], float(start_temp)
-    for turn in range(max(int(max_turns or 0), 1) + 2):
+    for turn in range(max(int(turns or max_turns or 0), 1) + 2):
         t = temp_fn(t, turn, max_turns)
         out.append(t)
     return np.asarray(out, dtype=np.float32)

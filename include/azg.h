@@ -48,7 +48,8 @@ typedef enum azg_game {
     AZG_GAME_BRANDUBH = 1,      /* alphazero/envs/brandubh/fastafl.pyx + fastafl/cengine.pyx         */
     AZG_GAME_TRIMOK = 2,        /* build-defined 3-player env (N-player path, BASELINE config 5)     */
     AZG_GAME_OTHELLO = 3,       /* alphazero/envs/othello/othello.pyx + OthelloLogic.pyx (ABI v7)    */
-    AZG_GAME_GOBANG = 4         /* alphazero/envs/gobang/gobang.pyx + GobangLogic.pyx (ABI v7)       */
+    AZG_GAME_GOBANG = 4,        /* alphazero/envs/gobang/gobang.pyx + GobangLogic.pyx (ABI v7)       */
+    AZG_GAME_TICTACTOE = 5      /* alphazero/envs/tictactoe/tictactoe.py + TicTacToeLogic.py (ABI v7) */
 } azg_game;
 
 /* Game state as it crosses the ABI (all games): the reference's board array, row-major, one int8 per cell
@@ -58,7 +59,9 @@ typedef enum azg_game {
  * Gobang's 15x15 board (225 cells) does not fit one byte per cell: its cells[64] hold two packed boards, 32 bytes each -- colour 1
  * (player 0) first, then colour -1 (player 1).  A board is four little-endian uint64 words of 15 rows x 16 bits: pieces[x][y]
  * (action a = 15x + y) is bit 16x + y, bit 15 of every row and bits 240..255 are zero.  aux is zero.  The Python layer
- * (engine.py) packs and unpacks, so its callers still see 225 int8 cells. */
+ * (engine.py) packs and unpacks, so its callers still see 225 int8 cells.
+ * Tic-tac-toe: cells[3x + y] = pieces[x][y] of TicTacToeLogic.py (1 = player 0's colour, -1 = player 1's, 0 = empty), cells 9..63 and
+ * aux zero; action a plays cell a.  Any assignment of the nine cells is accepted, reachable or not. */
 typedef struct azg_state {
     int8_t  cells[64];
     int32_t player;
@@ -394,7 +397,8 @@ int  azg_heads_softmax(void *stream, const float *logits_dev, int boards, int lo
 int  azg_tower_layout(int game, int boards_per_tile, int channels, int16_t *pixmap, int32_t *qrow, int32_t *info8);
 
 /* Which network launches are instantiated for (game, tower width): a mask of AZG_SUPPORT_* bits, from the same tile lists the launches
- * are built from (csrc/azg_tiles.h; no device needed).  AZG_E_INVALID_ARG for an unknown game. */
+ * are built from (csrc/azg_tiles.h; no device needed).  AZG_E_INVALID_ARG for an unknown game; AZG_E_UNSUPPORTED for tic-tac-toe at
+ * any width but 32, the only one that game is built for. */
 int  azg_launch_support(int game, int channels);
 #define AZG_SUPPORT_TOWER         1   /* the stand-alone MFMA tower: azg_resnet_tower_f16 / azg_resnet_tower_features_f16              */
 #define AZG_SUPPORT_SEARCH_WIDE   2   /* factorised heads, exact: azg_search_wide_exact_f16 and azg_search_arena_wide_exact_f16        */

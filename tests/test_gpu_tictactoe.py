@@ -1,0 +1,699 @@
+"""Tic-tac-toe on the device (csrc/azg_games.h struct TT, game id 5) against fixtures the REFERENCE produced (tests/golden/tt_*.npz, written
+by tests/golden/make_tictactoe_goldens.py from alphazero/envs/tictactoe) and the 3x3 network kernels against the fp64 reference of
+tests/net_reference.py:
+
+  * ALL 39 366 records of tt_rules (every board x both movers, unreachable ones included) through the engine ABI: valid moves, win state,
+    observation, and EVERY legal move of every undecided record by a steered second simulation (test_gpu_rules._check_records);
+  * the reference's MCTS (tt_tree: random and uniform priors; tt_edge: exact ties, zero and denormal priors, roots of one and two legal
+    moves), both per-phase launch forms; SelfPlayAgent (tt_agent: raw and symmetric samples, fast rounds, warm-up -- at a temperature
+    that never steps: max_turns() is None) and a whole agent under np.random.seed(s) (tt_mt19937_agent);
+  * the tower, head features with their zero padding, logits and probabilities of the default 32 x 4 net (16 + 16 head channels) and of
+    TICTACTOE_NET_ARGS (4 + 4, padded) at every tower tile -- one, five and sixteen boards -- and their ragged last tiles;
+  * azg_search_wide_exact_f16, azg_search_arena_wide_exact_f16 and azg_search_raw against the launch-per-phase loops, bit for bit;
+  * the MCTS class API with pickling, the launch mask against the launches, one self-play iteration and one arena through the runners."""
+import ctypes as C
+import os
+import pickle
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+import edge_eval as ee
+import net_reference as R
+import oracle_lib as ol
+import test_gpu_arena_wide as AW
+import test_gpu_net_fp64 as F
+import test_gpu_parity as P
+import test_gpu_raw_search as RS
+import test_gpu_rules as GR
+
+pytestmark = pytest.mark.gpu
+G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+TT, DEV, A, NV = 5, 'cuda:0', 9, 3
+NETS = {'tictactoe_32x4_h4': ('TICTACTOE_NET_ARGS', {}), 'tictactoe_32x4': ('DEFAULT_NET_ARGS', {})}
+
+
+def _game():
+    from alphazero_general_amd.envs.tictactoe import Game
+    return Game
+
+
+def _states(prefix):
+    Game = _game()
+    out = []
+    for row in prefix:
+        g = Game()
+        for a in row:
+            if a >= 0:
+                g.play_action(int(a))
+        out.append(g.to_azg_state())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------- rules
+@pytest.mark.parametrize('mover', [0, 1])
+@pytest.mark.parametrize('k', range(9))
+def test_tt_rules_every_state_every_move(k, mover):
+    """pass k plays the k-th legal move of every undecided record of `mover` that has one (pass 0 also holds every record's valid moves,
+    win state and observation: all 19 683 boards per mover); the successor of (record, action) is the record the reference's
+    play_action led to"""
+    import test_tictactoe_cpu as TC
+    d = TC.rules()
+    n = len(d['player'])
+    crc = np.array([GR.crc(o.astype(np.float32).reshape(1, 3, 3)) for o in d['obs']], np.uint32)
+    nleg = d['valids'].sum(1)
+    live = ~d['ws'].any(1) & (nleg > k) & (d['player'] == mover)
+    rec = np.flatnonzero(d['player'] == mover) if k == 0 else np.flatnonzero(live)
+    action = np.full(len(rec), -1, np.int64)
+    for j, r in enumerate(rec):
+        if live[r]:
+            action[j] = np.flatnonzero(d['valids'][r])[k]
+    succ_rec = np.array([d['succ'][r, a] if a >= 0 else -1 for r, a in zip(rec, action)])
+    extra = np.unique(succ_rec[succ_rec >= 0])
+    allrec = np.concatenate([rec, extra])
+    pos = {int(r): len(rec) + j for j, r in enumerate(extra)}
+    succ = np.array([pos[int(s)] if s >= 0 else -1 for s in succ_rec] + [-1] * len(extra))
+    action = np.concatenate([action, np.full(len(extra), -1, np.int64)])
+    got = GR._check_records(torch, TT, d['cells'][allrec], d['player'][allrec], d['turns'][allrec], None, d['valids'][allrec], d['ws'][allrec],
+                            crc[allrec], action, succ)
+    assert got == int(live.sum()) and (k > 0 or len(rec) == 3 ** 9)
+    assert k >= 8 or got > 0
+
+
+# ------------------------------------------------------------------------------------------------------------------------- tree
+TREE_CONFIGS = ['default', 'cpuct2', 'noise', 'noise_temp', 'uniform', 'uniform_noise_temp']
+
+
+def _tree_batch(cname, seed, R_, s, dev):
+    pol, val = P.fake_batch(torch, seed, range(R_), s, A, NV, dev)
+    if cname.startswith('uniform'):                            # (make_tictactoe_goldens.uniform_eval: float32(1) / float32(9), the random value row)
+        pol = torch.full((R_, A), float(np.float32(1.0) / np.float32(A)), dtype=torch.float32, device=dev)
+    return pol, val
+
+
+@pytest.mark.parametrize('cname', TREE_CONFIGS)
+def test_tt_tree_vs_reference_goldens(cname):
+    d = dict(np.load(os.path.join(G, 'tt_tree.npz')))
+    cpuct, fpu, noise, temp, sims = d[cname + '_cfg']
+    noise, temp, sims = bool(noise), bool(temp), int(sims)
+    seed = int(d[cname + '_seed'])
+    R_ = d['prefix'].shape[0]
+    assert 4 <= R_ <= 16 and 8 <= sims <= 30
+    exact = not temp
+    engs = [P.engine(game=TT, B=R_, cpuct=cpuct, fpu_reduction=fpu, add_root_noise=noise, add_root_temp=temp, seed=seed, sims_hint=sims)
+            for _ in range(2)]                                 # [0]: azg_select + azg_backup, [1]: azg_backup_select
+    try:
+        for e in engs:
+            e.set_states(_states(d['prefix']))
+        obs = [e.new_obs() for e in engs]
+        engs[1].select(obs[1])
+        for s in range(sims):
+            engs[0].select(obs[0])
+            assert torch.equal(obs[0], obs[1]), s
+            for r in range(R_):
+                for e in engs:
+                    path = e.last_path(r)
+                    assert len(path) == d[cname + '_depth'][r, s]
+                    assert (path[:24] == d[cname + '_paths'][r, s][:len(path)]).all(), (r, s)
+            pol, val = _tree_batch(cname, seed, R_, s, engs[0].device)
+            engs[0].backup(pol, val)
+            if s + 1 < sims:
+                engs[1].backup_select(pol, val, obs[1])
+            else:
+                engs[1].backup(pol, val)
+            for e in engs:
+                assert (e.root_counts().cpu().numpy() == d[cname + '_rootn'][:, s]).all(), s
+        for e in engs:
+            for r in range(R_):
+                ch = e.root_children(r)
+                k = len(ch['a'])
+                assert (ch['a'] == d[cname + '_a'][r][:k]).all() and (d[cname + '_a'][r][k:] == -1).all() and (ch['n'] == d[cname + '_n'][r][:k]).all()
+                for f in ('q', 'p', 'v'):
+                    if exact:
+                        assert (ch[f] == d[cname + '_' + f][r][:k]).all(), (f, r)
+                    else:
+                        assert np.allclose(ch[f], d[cname + '_' + f][r][:k], atol=1e-5), (f, r)
+                info = e.tree_info(r)
+                assert info['n'] == d[cname + '_root_n'][r] and info['max_depth'] == d[cname + '_maxdepth'][r]
+            assert (e.root_counts().cpu().numpy() == d[cname + '_counts']).all()
+            assert d['prob_temps'].tolist() == [1.0, 0.5, 0.25, float(np.float32(0.2)), 0.0]
+            for ti, t in enumerate(d['prob_temps']):
+                got, want = e.root_probs(float(t)).cpu().numpy(), d[cname + '_probs'][:, ti]
+                if float(t) in (1.0, 0.5, 0.0):                # (as the tree tests of the other games: exact where numpy's power is)
+                    assert (got == want).all(), t
+                else:
+                    assert np.allclose(got, want, rtol=3e-7, atol=1e-12), t
+            assert (e.root_value(False).cpu().numpy() == d[cname + '_vmax']).all()
+            assert (e.root_value(True).cpu().numpy() == d[cname + '_vavg']).all()
+            assert (e.tape_counters() == d[cname + '_ctr']).all()
+            e.counters()
+    finally:
+        for e in engs:
+            e.close()
+
+
+def _edge():
+    return ee.load(G, 'tt')
+
+
+def _edge_roots(d):
+    Game = _game()
+    return [Game.from_azg_state(d['cells'][r], int(d['player'][r]), int(d['turns'][r])) for r in range(len(d['player']))]
+
+
+def _check_probs(pr, d, cname, ti, t):
+    for r in range(len(pr)):
+        ref = d[cname + '_probs'][r][ti]
+        if d[cname + '_probs_raised'][r][ti]:
+            assert np.allclose(pr[r], ee.probs_untrapped(d[cname + '_counts'][r], t), rtol=3e-7, atol=1e-12, equal_nan=True), (r, t)
+        elif t in (1.0, 2.0, 0.5, 0.0):
+            assert (pr[r] == ref).all(), (r, t)
+        else:
+            assert np.allclose(pr[r], ref, rtol=3e-7, atol=1e-12), (r, t)
+
+
+@pytest.mark.parametrize('cname', ee.CONFIGS)
+def test_tt_edge_tree_vs_reference_goldens(cname):
+    """tests/test_gpu_tree_edges.py's check on tt_edge.npz: exact PUCT ties (uniform rows), zero priors (one-hot rows), denormal priors
+    (spread rows), cpuct 0 / 50, fpu_reduction -1 / 0, noise_frac 1, root temperatures 0.5 / 2 / 1.1, on random roots and on roots with
+    one legal move (one move from a full board) and two; both per-phase launch forms"""
+    from alphazero_general_amd.engine import DeviceEngine
+    d = _edge()
+    cpuct, fpu, nfrac, rtemp, sims = d[cname + '_cfg']
+    noise, temp, sims = bool(nfrac > 0), bool(rtemp > 0), int(sims)
+    fam, seed = str(d[cname + '_family']), int(d[cname + '_seed'])
+    exact = not temp or rtemp in (2.0, 0.5)
+    roots = _edge_roots(d)
+    R_ = len(roots)
+    ks = sorted(int(g.valid_moves().sum()) for g in roots)
+    assert 4 <= R_ <= 16 and 8 <= sims <= 30 and ks[:4] == [1, 1, 2, 2] and ks[-1] == 9
+    a_of = d[cname + '_a']
+    engs = [DeviceEngine(TT, R_, cpuct=float(cpuct), fpu_reduction=float(fpu), root_noise_frac=float(nfrac) if noise else 0.1,
+                         root_policy_temp=float(rtemp) if temp else 1.1, add_root_noise=noise, add_root_temp=temp, seed=seed,
+                         sims_hint=sims) for _ in range(2)]
+    try:
+        for e in engs:
+            e.set_states([g.to_azg_state() for g in roots])
+        engs[1].select(None)
+        for s in range(sims):
+            engs[0].select(None)
+            pol = np.zeros((R_, A), np.float32); val = np.zeros((R_, NV), np.float32)
+            for r in range(R_):
+                dep = int(d[cname + '_depth'][r, s])
+                ref = d[cname + '_paths'][r, s][:dep]
+                for e in engs:
+                    path = e.last_path(r)
+                    assert len(path) == dep and (path == ref).all(), (r, s)
+                pol[r], val[r] = ee.leaf_row(fam, seed, roots[r], r, s, ref, A, NV)
+                assert ee.row_crc(pol[r], val[r]) == d[cname + '_row_crc'][r, s], (r, s)
+            tp, tv = torch.from_numpy(pol).to(engs[0].device), torch.from_numpy(val).to(engs[0].device)
+            engs[0].backup(tp, tv)
+            if s + 1 < sims:
+                engs[1].backup_select(tp, tv, None)
+            else:
+                engs[1].backup(tp, tv)
+            want = np.zeros((R_, A), np.int32)
+            for r in range(R_):
+                k = int((a_of[r] >= 0).sum())
+                want[r, a_of[r][:k]] = d[cname + '_rootn'][r, s][:k]
+            for e in engs:
+                assert (e.root_counts().cpu().numpy() == want).all(), s
+        for e in engs:
+            for r in range(R_):
+                ch = e.root_children(r)
+                k = len(ch['a'])
+                assert (ch['a'] == a_of[r][:k]).all() and (a_of[r][k:] == -1).all()
+                assert (ch['n'] == d[cname + '_n'][r][:k]).all()
+                for f in ('q', 'p', 'v'):
+                    if exact:
+                        assert (ch[f] == d[cname + '_' + f][r][:k]).all(), (f, r)
+                    else:
+                        assert np.allclose(ch[f], d[cname + '_' + f][r][:k], atol=1e-5), (f, r)
+                info = e.tree_info(r)
+                assert info['n'] == d[cname + '_root_n'][r] and info['max_depth'] == d[cname + '_maxdepth'][r], r
+            assert (e.root_counts().cpu().numpy() == d[cname + '_counts']).all()
+            for ti, t in enumerate(d['prob_temps']):
+                _check_probs(e.root_probs(float(t)).cpu().numpy(), d, cname, ti, float(t))
+            assert (e.root_value(False).cpu().numpy() == d[cname + '_vmax']).all()
+            assert (e.root_value(True).cpu().numpy() == d[cname + '_vavg']).all()
+            assert (e.tape_counters() == d[cname + '_ctr']).all()
+            e.counters()
+    finally:
+        for e in engs:
+            e.close()
+
+
+def _zero_temp(cur_temp, turns, const_max_turns):
+    return 0
+
+
+@pytest.mark.parametrize('launch', P.LAUNCHES)
+def test_tt_edge_agent_vs_reference_goldens(launch):
+    """the edge agent of tt_edge.npz: uniform priors, draw-heavy values, temperature 0 from the first move (np.argmax ties over the visit
+    counts), symmetric samples on"""
+    from alphazero_general_amd.engine import DeviceEngine
+    d = _edge()
+    B, sims, games, seed = int(d['agent_B']), int(d['agent_sims']), int(d['agent_games']), int(d['agent_seed'])
+    assert 4 <= B <= 8
+    eng = DeviceEngine(TT, B, seed=seed, games_per_iteration=games, example_capacity=4096, sims_hint=sims, start_temp=0.0, temp_fn=_zero_temp)
+    try:
+        rec = dict(actions=[], counts=[], games_played=[], obs_crc=[])
+        step, gp = 0, 0
+        obs = eng.new_obs()
+        for _ in range(len(d['agent_actions'])):
+            assert gp < games
+            if launch == 'fused':
+                eng.select(obs)
+            for s in range(sims):
+                if launch == 'phase':
+                    eng.select(obs)
+                o = obs.cpu().numpy()
+                rec['obs_crc'].append([zlib.crc32(np.ascontiguousarray(o[i]).tobytes()) & 0xFFFFFFFF for i in range(B)])
+                pol = np.zeros((B, A), np.float32); val = np.zeros((B, NV), np.float32)
+                for i in range(B):
+                    pol[i], val[i] = ee.agent_row(seed, i, step, A, NV)
+                tp, tv = torch.from_numpy(pol).to(eng.device), torch.from_numpy(val).to(eng.device)
+                if launch == 'fused' and s + 1 < sims:
+                    eng.backup_select(tp, tv, obs)
+                else:
+                    eng.backup(tp, tv)
+                step += 1
+            rec['counts'].append(eng.root_counts().cpu().numpy())
+            eng.advance(record_history=True)
+            rec['actions'].append(eng.last_actions().cpu().numpy())
+            gp = eng.counters()['games_played']
+            rec['games_played'].append(gp)
+        assert gp == games
+        assert (np.array(rec['counts']) == d['agent_counts']).all() and (np.array(rec['actions']) == d['agent_actions']).all()
+        assert (np.array(rec['games_played']) == d['agent_games_played']).all()
+        assert (np.array(rec['obs_crc'], np.uint32) == d['agent_obs_crc']).all()
+        o, pi, z = [t.cpu().numpy() for t in eng.examples()]
+        assert o.shape == d['agent_s_obs'].shape and (o == d['agent_s_obs']).all() and (pi == d['agent_s_pi']).all() and (z == d['agent_s_z']).all()
+        ws, turns, _ = eng.results()
+        assert (ws == d['agent_r_ws']).all() and (turns == d['agent_r_turns']).all()
+    finally:
+        eng.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------- agent
+AGENT = {'plain': (dict(symmetric_samples=False), dict()),
+         'symmetric': (dict(add_root_noise=True, add_root_temp=True, cpuct=2.0), dict()),
+         'fastmix': (dict(symmetric_samples=False), dict(prob_fast=0.5, fast_sims=4)),
+         'warmup': (dict(), dict(warmup=True, warmup_sims=5))}
+
+
+@pytest.mark.parametrize('launch', P.LAUNCHES)
+@pytest.mark.parametrize('cname', list(AGENT))
+def test_tt_agent_vs_reference_goldens(cname, launch):
+    """whole reference SelfPlayAgent runs, move for move and sample for sample.  The engine's DEFAULT temperature schedule is used: the
+    fixture's moves are those of a temperature that stays at startTemp (the generator asserted that a schedule halving after every move
+    -- what azg_game_info.max_turns = 9 would give -- samples other moves from round `<config>_halving_differs_at` on)"""
+    d = dict(np.load(os.path.join(G, 'tt_agent.npz')))
+    B, sims, games = int(d[cname + '_B']), int(d[cname + '_sims']), int(d[cname + '_games'])
+    seed, slot_base = int(d[cname + '_seed']), int(d[cname + '_slot_base'])
+    assert 4 <= B <= 8
+    kw, rnd = AGENT[cname]
+    eng = P.engine(game=TT, B=B, seed=seed, slot_base=slot_base, games_per_iteration=games, example_capacity=4096, sims_hint=sims, **kw)
+    assert (eng._tt == np.float32(1.0)).all() and len(eng._tt) == 11
+    rec = P.run_engine_agent(torch, eng, seed, slot_base, sims, games, launch=launch, **rnd)
+    assert (np.array(rec['sims']) == d[cname + '_round_sims']).all()
+    assert (np.array(rec['counts']) == d[cname + '_counts']).all()
+    assert (np.array(rec['actions']) == d[cname + '_actions']).all()
+    assert (np.array(rec['games_played']) == d[cname + '_games_played']).all()
+    if cname != 'warmup':
+        assert (np.array(rec['obs_crc'], np.uint32) == d[cname + '_obs_crc']).all()
+    if cname in ('plain', 'symmetric'):
+        assert int(d[cname + '_halving_differs_at']) < len(rec['actions'])
+    obs, pi, z = [t.cpu().numpy() for t in eng.examples()]
+    assert obs.shape == d[cname + '_s_obs'].shape
+    assert (obs == d[cname + '_s_obs']).all() and (pi == d[cname + '_s_pi']).all() and (z == d[cname + '_s_z']).all()
+    ws, turns, _ = eng.results()
+    assert (ws == d[cname + '_r_ws']).all() and (turns == d[cname + '_r_turns']).all()
+    eng.close()
+
+
+@pytest.mark.parametrize('launch', P.LAUNCHES)
+def test_tt_selfplay_agent_under_numpys_mt19937_seed(launch):
+    d = dict(np.load(os.path.join(G, 'tt_mt19937_agent.npz')))
+    B, sims, games, eseed = int(d['B']), int(d['sims']), int(d['games']), int(d['eval_seed'])
+    cpuct, fpu, nfrac, rtemp = [float(x) for x in d['cfg']]
+    eng = P.engine(game=TT, B=B, cpuct=cpuct, fpu_reduction=fpu, root_noise_frac=nfrac, root_policy_temp=rtemp, add_root_noise=True,
+                   add_root_temp=True, seed=987654321, games_per_iteration=games, example_capacity=4096, sims_hint=sims)
+    eng.set_random_tape(d['tape_ranks'], d['tape_u'], d['tape_noise_off'], d['tape_noise_pool'])
+    rec = P.run_engine_agent(torch, eng, eseed, 0, sims, games, launch=launch)
+    n = len(d['actions'])
+    assert len(rec['actions']) == n and (np.array(rec['games_played']) == d['games_played']).all()
+    for r in range(n):
+        assert (np.asarray(rec['counts'][r]) == d['counts'][r]).all(), (launch, r)
+        assert (np.asarray(rec['actions'][r]) == d['actions'][r]).all(), (launch, r)
+    eo, ep, ez = [t.cpu().numpy() for t in eng.examples()]
+    assert eo.shape == d['s_obs'].shape and (eo == d['s_obs']).all() and (ez == d['s_z']).all() and (ep == d['s_pi']).all()
+    ws, turns, _ = eng.results()
+    assert (ws == d['r_ws']).all() and (turns == d['r_turns']).all()
+    eng.set_shuffle_tape(None)
+    eng.close()
+
+
+def test_tt_mcts_class_api_vs_reference_goldens_with_pickling():
+    """alphazero_general_amd.MCTS on an envs.tictactoe.Game object (one slot: the tape stream of tt_tree's root 0 -- the empty board),
+    find_leaf / process_results fed the fixture's evaluations, pickled and restored half way, must build the reference's tree"""
+    from alphazero_general_amd.MCTS import MCTS
+    from alphazero_general_amd.utils import dotdict
+    d = dict(np.load(os.path.join(G, 'tt_tree.npz')))
+    cpuct, fpu, _, _, sims = d['default_cfg']
+    seed, sims = int(d['default_seed']), int(sims)
+    g = _game().from_azg_state(*_states(d['prefix'][:1])[0])
+    m = MCTS(dotdict(cpuct=float(cpuct), fpu_reduction=float(fpu), root_noise_frac=0.1, root_policy_temp=1.1, min_discount=1,
+                     _num_players=3, numMCTSSims=sims, _azg_seed=seed))
+    for s in range(sims):
+        if s == sims // 2:
+            m = pickle.loads(pickle.dumps(m))
+        leaf = m.find_leaf(g)
+        assert m.depth == d['default_depth'][0, s] and type(leaf) is _game()
+        p, v = ol.fake_eval(seed, 0, s, A, NV)
+        m.process_results(leaf, v, p, False, False)
+    assert (np.asarray(m.counts(g)) == d['default_counts'][0]).all()
+    assert m.value(False) == d['default_vmax'][0] and m.value(True) == d['default_vavg'][0]
+    assert (np.asarray(m.probs(g, 1.0), np.float32) == d['default_probs'][0, 0]).all()
+    a = m.best_action(g)
+    m.update_root(g, a)
+    g.play_action(a)
+    assert int(np.asarray(m.counts(g)).sum()) > 0
+
+
+# ------------------------------------------------------------------------------------------------------------------------- network
+def boards(n=301, seed=0):
+    """n boards [n, 1, 3, 3] float32 (net_reference.boards needs a turn limit to size its playouts): the empty board, all ones, all
+    minus ones, then records of tt_rules drawn without replacement -- full boards, won boards and unreachable ones among them"""
+    d = np.load(os.path.join(G, 'tt_rules.npz'))
+    rng = np.random.RandomState(seed)
+    pick = rng.choice(3 ** 9, n - 3, replace=False) * 2
+    x = np.concatenate([np.zeros((1, 9)), np.ones((1, 9)), -np.ones((1, 9)), d['obs'][pick]]).astype(np.float32)
+    return x.reshape(n, 1, 3, 3)
+
+
+def _reference(key, salt=0, depth=None):
+    argname, over = NETS[key]
+    over = dict(over)
+    if depth is not None:
+        over['depth'] = depth
+    args = R.net_args(argname, **over)
+    x = torch.from_numpy(boards())
+    sd, ref = R.make_state('tictactoe', args, 'trained', salt, probe=x)
+    return args, sd, ref, x, ref.forward(x)
+
+
+def _wrapper(args, sd):
+    from alphazero_general_amd.nnet import NNetWrapper
+    net = NNetWrapper(_game(), args, device=DEV, backend='hip')
+    net.adopt(sd)
+    net.refresh()
+    assert net._hip is not None and net._hip.fact_head and net._hip.can_search and net._hip.search_preferred
+    return net
+
+
+def _tile(n, cus):
+    """boards per workgroup tile dispatch_tower picks for tic-tac-toe x 32"""
+    return 1 if n <= 8 * cus else 5 if n <= 80 * cus else 16
+
+
+def _check(name, args, sd, ref, o, x, sizes):
+    net = _wrapper(args, sd)
+    hip = net._hip
+    vc, pc = ref.vc, ref.head_w.shape[0] - ref.vc
+    N = x.shape[0]
+    xg = x.to(DEV)
+    for B in sizes:
+        idx = F._idx(N, B)
+        xb = xg[idx.to(DEV)].contiguous()
+        x8 = hip.to_nhwc8(xb)
+        tag = '%s_B%d' % (name, B)
+        F._stream_cmp(tag, hip, F.tower_stream(hip, x8), o, idx, _tile(B, F._cus()))
+        feat = hip.forward_features_nhwc8(x8).float().cpu().reshape(B, 2, hip.feat_k)
+        assert hip.feat_k == 160 and float(feat[:, :, 144:].abs().max()) == 0.0                  # the rows' padding behind 9 x 16 features
+        f = feat[:, :, :144].reshape(B, 2, 9, 16)                                                # [B, policy | value, pos, 16]
+        assert float(f[:, 0, :, pc:].abs().max() if pc < 16 else 0.0) == 0.0                     # the padded head channels: exact zeros
+        assert float(f[:, 1, :, vc:].abs().max() if vc < 16 else 0.0) == 0.0
+        got = torch.cat([f[:, 1, :, :vc], f[:, 0, :, :pc]], 2).permute(0, 2, 1).reshape(B, vc + pc, 3, 3)   # value channels, then policy
+        sel = F._sel(B)
+        rep = R.stream_report(got[sel], o['feat'][idx[sel]], tile=1)
+        F.record(dict(case=tag, what='head_features', **rep, tau=R.TAU_STREAM))
+        assert rep['ratio'] <= 1.0, (tag, rep)
+        lg = hip.forward_logits_nhwc8(x8).float().cpu()
+        F._logits_cmp(tag + '_fact', lg[:, :hip.A], lg[:, hip.A:hip.A + hip.NV], o, idx)
+        p, v = net.process(xb)
+        F._probs_cmp(tag + '_process', p.cpu(), v.cpu(), o, idx)
+
+
+@pytest.mark.parametrize('key', list(NETS))
+def test_tt_network_every_tile_vs_fp64(key):
+    """the one-board tile at 1, 2, 16, 17, 33 boards; the five-board tile from 8 boards per CU + 1 (a ragged last tile, as + 2 ... + 5 are
+    whole or ragged in turn); the sixteen-board tile from 80 per CU + 1 and at + 17, + 33 (one and two whole tiles more, ragged)"""
+    args, sd, ref, x, o = _reference(key)
+    cus = F._cus()
+    sizes = [1, 2, 16, 17, 33, 8 * cus, 8 * cus + 1, 8 * cus + 5, 8 * cus + 6, 80 * cus, 80 * cus + 1, 80 * cus + 16, 80 * cus + 17, 80 * cus + 33]
+    assert {_tile(n, cus) for n in sizes} == {1, 5, 16}
+    _check(key, args, sd, ref, o, x, sizes)
+
+
+@pytest.mark.parametrize('depth', [1, 6])
+@pytest.mark.parametrize('key', list(NETS))
+def test_tt_network_depths_vs_fp64(key, depth):
+    args, sd, ref, x, o = _reference(key, depth=depth)
+    cus = F._cus()
+    _check('%s_depth%d' % (key, depth), args, sd, ref, o, x, [17, 8 * cus + 1, 80 * cus + 17])
+
+
+# ------------------------------------------------------------------------------------------------------------------------- search launches
+def _net(key, salt=7):
+    args, sd, ref, x, o = _reference(key, salt=salt)
+    return _wrapper(args, sd)
+
+
+def _twin_search(net, B, sims, moves, states=None, **kw):
+    """azg_search_wide_exact_f16 against select -> NNetWrapper.process -> backup on a twin engine with the same seeds: every slot's counts,
+    probabilities, values, moves, samples and results identical"""
+    from alphazero_general_amd.engine import DeviceEngine
+    kw = dict(dict(seed=41, games_per_iteration=1 << 30, example_capacity=B * (moves + 1) * 8, sims_hint=sims), **kw)
+    ea, ec = DeviceEngine(TT, B, **kw), DeviceEngine(TT, B, **kw)
+    try:
+        if states is not None:
+            ea.set_states(states); ec.set_states(states)
+        oc = ec.new_obs(torch.float32)
+        for mv in range(moves):
+            net._hip.search(ea, sims, exact=True)
+            for _ in range(sims):
+                ec.select(oc)
+                p, v = net.process(oc)
+                ec.backup(p.contiguous(), v.contiguous())
+            assert torch.equal(ea.root_counts(), ec.root_counts()), mv
+            assert torch.equal(ea.root_probs(1.0), ec.root_probs(1.0)) and torch.equal(ea.root_value(True), ec.root_value(True)), mv
+            assert torch.equal(ea.root_value(False), ec.root_value(False)), mv
+            ea.advance(True); ec.advance(True)
+            assert torch.equal(ea.last_actions(), ec.last_actions()), mv
+        assert (ea.tape_counters() == ec.tape_counters()).all()
+        assert ea.counters() == ec.counters() and ea.counters()['sims'] == B * sims * moves
+        for t, u in zip(ea.examples(), ec.examples()):
+            assert torch.equal(t, u)
+        assert all((a == b).all() for a, b in zip(ea.results(), ec.results()))
+        return net._hip.search_tile(ea, exact=True)
+    finally:
+        ea.close(); ec.close()
+
+
+@pytest.mark.parametrize('B', [1, 2, 3, 'wide'])
+@pytest.mark.parametrize('key', list(NETS))
+def test_tt_wide_exact_search_vs_phase_loop(key, B, capsys):
+    """slots = 1, the tile sizes 1 and 2 and one more than each (1, 2, 3): the one-game tile's helper wavefront and pixel groups 2, 3 of
+    the two-game tile own no subtile, and an odd engine leaves the last two-game tile one game short.  Which tile a launch takes is the
+    set-up's choice (azg_search_wide_tile_info); 'wide' is an odd engine past two games per CU, where the tile model's prior is the
+    two-game tile"""
+    n = 2 * F._cus() + 3 if B == 'wide' else B
+    tile = _twin_search(_net(key), n, 16, 3, cpuct=2.0, fpu_reduction=0.2, add_root_noise=True, add_root_temp=True)
+    assert tile is not None and tile['games_per_workgroup'] in (1, 2)
+    with capsys.disabled():
+        print('tictactoe %s, %d slots: %d game(s) per workgroup (%s)' % (key, n, tile['games_per_workgroup'], tile['source']))
+
+
+@pytest.mark.parametrize('key', list(NETS))
+def test_tt_wide_exact_search_at_exact_ties_from_the_edge_roots(key):
+    """the persistent launch where every PUCT comparison ties: the trained fill with the last Linear of both heads zeroed, so every logit
+    is 0, every prior the same after masking and every value row uniform -- on the roots of tt_edge.npz (one and two legal moves among
+    them), against the per-phase loop on a twin engine.  Root noise and temperature off."""
+    from alphazero_general_amd.engine import DeviceEngine
+    args, sd, ref, x, o = _reference(key, salt=7)
+    last = ['%s.%d' % (h, max(int(k.split('.')[1]) for k in sd if k.startswith(h + '.'))) for h in ('pi_fc', 'v_fc')]
+    sd = {k: (torch.zeros_like(v) if k.rsplit('.', 1)[0] in last else v) for k, v in sd.items()}
+    assert sum(1 for k in sd if k.rsplit('.', 1)[0] in last) == 4
+    net = _wrapper(args, sd)
+    roots = _edge_roots(_edge())
+    states = [g.to_azg_state() for g in roots]
+    ep = DeviceEngine(TT, len(states), seed=47)
+    ep.set_states(states)
+    oc = ep.new_obs(torch.float32)
+    ep.select(oc)
+    p, v = net.process(oc)                                  # the network really ties: every row's entries are equal bit for bit
+    ep.close()
+    assert p.shape == (len(states), A) and bool((p == p[:, :1]).all()) and bool((v == v[:, :1]).all()) and bool((p > 0).all())
+    _twin_search(net, len(states), 16, 3, states=states, seed=47, cpuct=1.25, fpu_reduction=-1.0)
+
+
+def _tt_nets(n, key='tictactoe_32x4_h4', seed0=20):
+    from alphazero_general_amd import nnet as N
+    na = R.net_args(NETS[key][0])
+    out = []
+    for m in range(n):
+        torch.manual_seed(seed0 + m)
+        w = N.NNetWrapper(_game(), na, device=DEV, dtype=torch.float16)
+        w.refresh()
+        out.append(w)
+    return out
+
+
+@pytest.mark.parametrize('raw', [False, True])
+@pytest.mark.parametrize('B', [2, 5])
+def test_tt_wide_arena_equals_host_split(B, raw):
+    """azg_search_arena_wide_exact_f16 (graph-captured and eager) plays exactly the games the host-split arena plays, two nets or a net
+    and a raw seat; slot 0's first game is replayed on the host env: every move legal, the game over exactly at its last move, the
+    recorded result the host's win state"""
+    nets = _tt_nets(1 if raw else 2)
+    seats = nets + [None] if raw else nets
+    runs = AW._forms(_game(), seats, AW._args(), B, 5 + B, 'slot', 15)
+    AW._same(runs)
+    acts, _, (ws, turns, slot), _ = runs[0]
+    first = int(np.flatnonzero(slot == 0)[0])
+    g = _game()()
+    for rnd in range(int(turns[first])):
+        a = int(acts[rnd][0])
+        assert not g.win_state().any() and g.valid_moves()[a] == 1, rnd
+        g.play_action(a)
+    assert g.turns == turns[first] and g.win_state().any() and (g.win_state() == ws[first]).all()
+
+
+@pytest.mark.parametrize('consts', [RS.RAW, RS.WARM])
+@pytest.mark.parametrize('B', [1, 3, 64])
+def test_tt_search_raw_equals_per_phase_loop(B, consts):
+    sims, rounds = 20, 12
+    mk = lambda: RS._engine(TT, B, seed=36, sims_hint=sims, add_root_noise=True, add_root_temp=True, cpuct=4.0, fpu_reduction=0.4,
+                            example_capacity=B * (rounds + 1) * 8)
+    ea, eb = mk(), mk()
+    try:
+        fill, vrow = RS._rows(ea, consts)
+        pol = torch.full((B, A), fill, dtype=torch.float32, device=eb.device)
+        val = torch.from_numpy(np.tile(vrow, (B, 1))).to(eb.device)
+        for rnd in range(rounds):
+            ea.search_raw(sims, fill, vrow)
+            for _ in range(sims):
+                eb.select(None)
+                eb.backup(pol, val)
+            assert RS._snapshot(ea) == RS._snapshot(eb), rnd
+            ea.advance(True); eb.advance(True)
+            assert torch.equal(ea.last_actions(), eb.last_actions()), rnd
+        ca, cb = ea.counters(), eb.counters()
+        assert ca == cb and ca['sims'] == B * sims * rounds and ca['games_played'] >= B      # games ended and restarted
+        for x, y in zip(ea.examples(), eb.examples()):
+            assert torch.equal(x, y)
+        for x, y in zip(ea.results(), eb.results()):
+            assert (x == y).all()
+    finally:
+        ea.close(); eb.close()
+
+
+@pytest.mark.parametrize('ch', [32, 64, 128])
+def test_tt_launches_exist_exactly_where_the_mask_says(ch):
+    """tests/test_gpu_launch_support.py's check for game id 5: the set-up call of the persistent launch (exact; sparse: never -- the mask
+    has no sparse bit for this game) and a stand-alone tower launch succeed exactly where azg_launch_support has their bit"""
+    from alphazero_general_amd import _abi, nnet as N
+    from alphazero_general_amd.engine import DeviceEngine
+    from alphazero_general_amd.utils import dotdict
+    L = _abi.lib()
+    mask = _abi.launch_support(TT, ch)                         # (the library refuses every width but 32 for this game: read as no launch)
+    assert mask == (_abi.SUPPORT_TOWER | _abi.SUPPORT_SEARCH_WIDE if ch == 32 else 0)
+    assert L.azg_launch_support(TT, ch) == (mask if ch == 32 else _abi.E_UNSUPPORTED)
+    torch.manual_seed(3)
+    na = dotdict(dict(N.TICTACTOE_NET_ARGS)); na['num_channels'] = ch; na['depth'] = 1
+    w = N.NNetWrapper(_game(), na, device=DEV, dtype=torch.float16, backend='torch')
+    h = N.HipResNet(N.FoldedResNet(w.nnet).to(DEV), TT, DEV)
+    assert (h.fact_head and h.feat_k == 160) or (ch == 128 and h.fused_head)    # (12 outputs fuse behind a 128-channel tower: no factorised operands)
+    dummy = torch.zeros(64, device=DEV)
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    op = lambda a: vp(getattr(h, a, dummy))
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    tower = (vp(h.tower_w), vp(h.tower_b), vp(h.tower_ps), vp(h.tower_pt))
+    want = lambda bit: 0 if mask & bit else _abi.E_UNSUPPORTED
+    e = DeviceEngine(TT, 2)
+    try:
+        assert L.azg_search_wide_exact_f16(e.h, st, *tower, 1, ch, op('head1_w'), op('head1_b'), op('head2_wps'), op('head2_wv'), op('head2_b'),
+                                           160, 0) == want(_abi.SUPPORT_SEARCH_WIDE)
+        assert L.azg_search_wide_f16(e.h, st, *tower, 1, ch, op('head1_w'), op('head1_b'), op('head_rows'), op('head2_b'), 160, 0) == _abi.E_UNSUPPORTED
+        x = torch.zeros((2, 9, 8), dtype=torch.float16, device=DEV)
+        y = torch.empty((2 * 9, ch), dtype=torch.float16, device=DEV)
+        assert L.azg_resnet_tower_f16(st, TT, vp(x), *tower, vp(y), 2, 1, ch) == want(_abi.SUPPORT_TOWER)
+        feat = torch.zeros((2, 2 * 160), dtype=torch.float16, device=DEV)
+        lg = torch.zeros((2, 16), dtype=torch.float32, device=DEV)
+        assert L.azg_leaf_heads_sparse_f16(e.h, st, vp(feat), 160, op('head_rows'), op('head2_b'), None, vp(lg), 16) == _abi.E_UNSUPPORTED
+        torch.cuda.synchronize()
+        e.counters()
+    finally:
+        e.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------- runners
+def _run_args(**kw):
+    from alphazero_general_amd.nnet import TICTACTOE_NET_ARGS
+    from alphazero_general_amd.utils import dotdict, default_temp_scaling
+    a = dotdict(TICTACTOE_NET_ARGS)
+    a.update(numMCTSSims=12, numFastSims=4, numWarmupSims=5, probFastSim=0.5, gamesPerIteration=32, cpuct=2.0, fpu_reduction=0.2,
+             root_noise_frac=0.25, root_policy_temp=1.1, min_discount=1.0, add_root_noise=True, add_root_temp=True, symmetricSamples=True,
+             mctsResetThreshold=None, startTemp=1.0, arenaTemp=0.25, temp_scaling_fn=default_temp_scaling, use_draws_for_winrate=True,
+             model_gating=False, workers=2, process_batch_size=16, arena_batch_size=16, arenaCompare=24, numIters=1, numWarmupIters=0,
+             _azg_seed=9)
+    a.update(kw)
+    return a
+
+
+def test_tt_one_iteration_and_one_arena_through_the_runners():
+    """run_iteration (SelfPlayRunner, train.py's cpuct and probFastSim) and run_arena (ArenaRunner) on 16 slots: the games end, the
+    samples are whole (8 symmetries of every recorded position, policies that sum to one over empty cells, one-hot results)"""
+    from alphazero_general_amd import iteration as I
+    args = _run_args()
+    net = _tt_nets(1)[0]
+    out = I.run_iteration(_game(), net, args, 1, num_slots=16)
+    obs, pi, z = [t.cpu() for t in out['samples']]
+    assert out['games'] >= 32 and sum(out['wins']) + out['draws'] == out['num_results'] >= 32
+    assert obs.shape[1:] == (1, 3, 3) and obs.shape[0] == pi.shape[0] == z.shape[0] and obs.shape[0] % 8 == 0 and obs.shape[0] >= 64
+    assert torch.allclose(pi.sum(1), torch.ones(pi.shape[0]), atol=1e-5) and bool((z.sum(1) == 1).all())
+    assert bool((pi[obs.reshape(-1, 9) != 0] == 0).all())                                    # no mass on a taken cell
+    assert bool(((obs == 0) | (obs == 1) | (obs == -1)).all())
+    nets = _tt_nets(2)
+    wins, draws, wr = I.run_arena(_game(), nets, args, 24, num_slots=16)
+    assert len(wins) == 2 and sum(wins) + draws >= 24 and abs(sum(wr) - 1) < 1e-9
+
+
+class _RefLikeNet:
+    def __init__(self, seed, args):
+        from alphazero_general_amd.nnet import ResNet
+        from alphazero_general_amd.utils import dotdict
+        torch.manual_seed(seed)
+        self.args = dotdict(args)
+        self.nnet = ResNet(_game().observation_size(), A, NV, self.args).cuda()
+
+
+def test_tt_native_coach_round(tmp_path):
+    """coach.native_coach on the stand-in Coach of tests/test_gpu_iteration.py: one network iteration of the game native_coach used to
+    refuse ("has no device rules"), 16 slots, then the gating arena"""
+    import test_gpu_iteration as TI
+    from alphazero_general_amd.coach import native_coach
+    args = _run_args(data=str(tmp_path / 'data'), run_name='tt', _azg_slots=16, _azg_arena_slots=16)
+    Native = native_coach(TI._StandInCoach)
+    coach = Native(_game(), _RefLikeNet(4, args), args)
+    coach.past_net = _RefLikeNet(5, args)
+    coach.learn()
+    assert len(coach.loaded) == 1
+    d, p, v = coach.loaded[0]
+    assert d.shape[0] == p.shape[0] == v.shape[0] >= 64 and d.shape[1:] == (1, 3, 3) and not d.is_cuda
+    assert torch.allclose(p.sum(1), torch.ones(p.shape[0]), atol=1e-5) and bool((v.sum(1) == 1).all())
+    for wins, draws, wr in coach.arena_results:
+        assert len(wins) == 2 and sum(wins) + draws >= 24 and len(wr) == 2 and abs(sum(wr) - 1) < 1e-9
