@@ -114,7 +114,8 @@ class GameState:
 
 # (the reference's own tictactoe class is NOT listed: behind install() it keeps going to the reference's classes, the fall-through env
 #  that tests/test_install_conformance.py pins; the device game is this package's envs.tictactoe.Game)
-_REFERENCE_ENVS = {'envs.connect4.connect4': 0, 'envs.brandubh.fastafl': 1, 'envs.othello.othello': 3, 'envs.gobang.gobang': 4}
+_REFERENCE_ENVS = {'envs.connect4.connect4': 0, 'envs.brandubh.fastafl': 1, 'envs.othello.othello': 3, 'envs.gobang.gobang': 4,
+                   'envs.hnefatafl.fastafl': 6}
 # device games whose class reports max_turns() None (the reference's default, Game.py:56-58): scale_temp never steps for them
 # (utils.py:19-23).  The value is the longest game: what azg_game_info.max_turns sizes history and paths with, and the number of turns a
 # temperature table has to cover -- never the schedule's max_turns argument.

@@ -34,6 +34,8 @@ def encode_state(gs):
         return np.asarray(gs._board.pieces, np.int8).reshape(-1), gs.player, gs.turns
     if gid == 4:                   # the reference's own gobang Game (envs/gobang/gobang.pyx:41-50): pieces[x][y] -> cells[15x + y]
         return np.asarray(gs._board.pieces, np.int8).reshape(-1), gs.player, gs.turns
+    if gid == 6:                   # the reference's own hnefatafl Game (envs/hnefatafl/fastafl.pyx:122-132): the same fastafl Board as brandubh, 11x11
+        return np.asarray(gs._board._state, np.int8).reshape(-1), gs.player, gs.turns, int(gs._board._king_captured)
     raise NotImplementedError('cannot encode %r for the device engine' % type(gs))
 
 
@@ -46,7 +48,7 @@ def decode_state(template, cells, player, turns, aux0=0):
         except TypeError:
             return cls.from_azg_state(cells, player, turns)
     g = template.clone()
-    if hasattr(g._board, '_state'):                            # the reference's brandubh Game: fastafl Board (boardgame/board.pxd:31-40)
+    if hasattr(g._board, '_state'):                            # the reference's brandubh / hnefatafl Game: fastafl Board (boardgame/board.pxd:31-40)
         shape = np.asarray(template._board._state).shape
         g._board._state = np.asarray(cells, np.uint8).reshape(shape).copy()
         g._board.num_turns = int(turns)
@@ -186,7 +188,8 @@ class MCTS:
             # ONE tree: its node store holds a whole game's worth of expansions (max_turns moves x the simulations per move x
             # max_children) -- more than a search that drops nothing could fill -- but at most NODE_STORE_BUDGET bytes (several MCTS
             # objects live side by side: one per arena player, one per agent): connect4 2.4 MB; brandubh at 200 simulations would be
-            # 123 MB, at 1600 simulations it is clamped to 256 MB (13 moves' worth).  args._azg_nodes_per_tree overrides.  A caller
+            # 123 MB, at 1600 simulations it is clamped to 256 MB (13 moves' worth); hnefatafl (512 turns x 448 children) is always
+            # clamped: 46 moves' worth at 200 simulations.  args._azg_nodes_per_tree overrides.  A caller
             # that keeps searching at ONE root is served by the forced compaction in find_leaf / search until the LIVE subtree
             # itself exceeds the store (AZG_E_TREE_FULL; the reference's limit there is host memory)
             gi = _abi.game_info(gid)

@@ -20,7 +20,7 @@ def install():
     (Coach.py, Arena.pyx) resolve here.  Call before importing alphazero.Coach / alphazero.Arena.  See INTEGRATION.md.
 
     Dispatch is per GAME (SURVEY.md 8b "Game plugin"): a game with device rule kernels (Game.azg_game_id) is searched by this
-    engine; for any other env of the reference (tictactoe, tafl boards larger than 7x7, ...) the classes registered here hand over to the
+    engine; for any other env of the reference (tictactoe, stratego, ...) the classes registered here hand over to the
     REFERENCE'S OWN alphazero.MCTS.MCTS / alphazero.SelfPlayAgent.SelfPlayAgent (reference_class), so those envs keep working
     exactly as before -- this package contains no CPU search."""
     import importlib

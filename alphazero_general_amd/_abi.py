@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('AZG_LIB_PATH') or os.path.join(HERE, 'lib', 'libazg_hip.so')   # (override: measurement builds)
 ABI_VERSION = 7
 
-GAME_CONNECT4, GAME_BRANDUBH, GAME_TRIMOK, GAME_OTHELLO, GAME_GOBANG, GAME_TICTACTOE = 0, 1, 2, 3, 4, 5
+GAME_CONNECT4, GAME_BRANDUBH, GAME_TRIMOK, GAME_OTHELLO, GAME_GOBANG, GAME_TICTACTOE, GAME_HNEFATAFL = 0, 1, 2, 3, 4, 5, 6
 E_INVALID_ARG, E_HIP, E_INVALID_ACTION, E_TREE_FULL, E_EXAMPLES_FULL, E_UNSUPPORTED, E_INTERNAL, E_FLOATING_POINT = -1, -2, -3, -4, -5, -6, -7, -8
 SUPPORT_TOWER, SUPPORT_SEARCH_WIDE, SUPPORT_SEARCH_SPARSE, SUPPORT_SEARCH_FUSED = 1, 2, 4, 8      # azg_launch_support
 ERROR_NAMES = {-1: 'AZG_E_INVALID_ARG', -2: 'AZG_E_HIP', -3: 'AZG_E_INVALID_ACTION', -4: 'AZG_E_TREE_FULL',
@@ -210,11 +210,39 @@ def gobang_unpack(raw):
     return out.reshape(-1)
 
 
+# hnefatafl's azg_state.cells (include/azg.h): two cells per byte, cell c = 11y + x in the low nibble of byte c / 2 for even c, the high
+# nibble for odd c; bytes 61..63 zero
+HNEFATAFL_CELLS = 121
+
+
+def hnefatafl_pack(cells):
+    """121 int8 cells (piece codes 0..8) -> the 64 bytes of azg_state.cells"""
+    c = np.zeros(128, np.uint8)
+    c[:HNEFATAFL_CELLS] = np.asarray(cells, np.int8).reshape(-1).astype(np.uint8) & 15
+    return (c[0::2] | (c[1::2] << 4)).astype(np.uint8).view(np.int8)
+
+
+def hnefatafl_unpack(raw):
+    """the 64 bytes of azg_state.cells -> 121 int8 cells"""
+    raw = np.frombuffer(bytes(raw), np.uint8)
+    out = np.zeros(128, np.int8)
+    out[0::2], out[1::2] = raw & 15, raw >> 4
+    return out[:HNEFATAFL_CELLS].copy()
+
+
 def cells_to_state(game, cells):
     """a board as Python callers hold it -> the int8 array that goes into azg_state.cells (at most 64 entries)"""
-    return gobang_pack(cells) if game == GAME_GOBANG else np.asarray(cells, np.int8).reshape(-1)
+    if game == GAME_GOBANG:
+        return gobang_pack(cells)
+    if game == GAME_HNEFATAFL:
+        return hnefatafl_pack(cells)
+    return np.asarray(cells, np.int8).reshape(-1)
 
 
 def state_cells(s, game, cells):
     """azg_state.cells -> the board as Python callers hold it (`cells` entries)"""
-    return gobang_unpack(bytes(s.cells)) if game == GAME_GOBANG else state_to_np(s, cells)
+    if game == GAME_GOBANG:
+        return gobang_unpack(bytes(s.cells))
+    if game == GAME_HNEFATAFL:
+        return hnefatafl_unpack(bytes(s.cells))
+    return state_to_np(s, cells)

@@ -34,7 +34,7 @@ def _ours(game_cls):
     from .Game import azg_game_id
     if not has_device_rules(game_cls):
         return None
-    return importlib.import_module(__package__ + '.envs.' + ('connect4', 'brandubh', 'trimok', 'othello', 'gobang', 'tictactoe')[azg_game_id(game_cls)]).Game
+    return importlib.import_module(__package__ + '.envs.' + ('connect4', 'brandubh', 'trimok', 'othello', 'gobang', 'tictactoe', 'hnefatafl')[azg_game_id(game_cls)]).Game
 
 
 class _NetCache:

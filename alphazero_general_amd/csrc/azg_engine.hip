@@ -52,8 +52,9 @@ static const azg_game_info k_info[] = {
     {OT::A, OT::OBS_C, OT::H, OT::W, OT::P, OT::HAS_DRAW, OT::MAX_TURNS, OT::NSYM, OT::CELLS, OT::MAXK},
     {GB::A, GB::OBS_C, GB::H, GB::W, GB::P, GB::HAS_DRAW, GB::MAX_TURNS, GB::NSYM, GB::CELLS, GB::MAXK},
     {TT::A, TT::OBS_C, TT::H, TT::W, TT::P, TT::HAS_DRAW, TT::MAX_TURNS, TT::NSYM, TT::CELLS, TT::MAXK},
+    {HN::A, HN::OBS_C, HN::H, HN::W, HN::P, HN::HAS_DRAW, HN::MAX_TURNS, HN::NSYM, HN::CELLS, HN::MAXK},
 };
-static const int k_num_games = 6;
+static const int k_num_games = 7;
 
 extern "C" int azg_abi_version(void) { return AZG_ABI_VERSION; }
 #ifndef AZG_SRC_SHA
@@ -101,10 +102,11 @@ template <typename T> static int dalloc(azg_engine *e, T **p, size_t count) {
     case AZG_GAME_OTHELLO: { using G = OT; CALL; } break; \
     case AZG_GAME_GOBANG: { using G = GB; CALL; } break; \
     case AZG_GAME_TICTACTOE: { using G = TT; CALL; } break; \
+    case AZG_GAME_HNEFATAFL: { using G = HN; CALL; } break; \
     default: return fail(AZG_E_UNSUPPORTED, "game has no device rules"); }
 // the same for the sparse heads (head features -> logits of the leaf's children only): not built for gobang, where nearly every
 // cell is a legal move, so a sparse row saves little and the 3616-wide feature dot products would spill, nor for tic-tac-toe, whose
-// nine logits are one output subtile either way
+// nine logits are one output subtile either way, nor for hnefatafl, which has no network launch at all
 #define SPARSE_GAME_SWITCH(e, CALL) \
     switch ((e)->cfg.game) { \
     case AZG_GAME_CONNECT4: { using G = C4; CALL; } break; \
@@ -113,6 +115,7 @@ template <typename T> static int dalloc(azg_engine *e, T **p, size_t count) {
     case AZG_GAME_OTHELLO: { using G = OT; CALL; } break; \
     case AZG_GAME_GOBANG: return fail(AZG_E_UNSUPPORTED, "no sparse heads for gobang (use the dense heads)"); \
     case AZG_GAME_TICTACTOE: return fail(AZG_E_UNSUPPORTED, "no sparse heads for tic-tac-toe (use the dense heads)"); \
+    case AZG_GAME_HNEFATAFL: return fail(AZG_E_UNSUPPORTED, "no sparse heads for hnefatafl (use the dense heads)"); \
     default: return fail(AZG_E_UNSUPPORTED, "game has no device rules"); }
 // dispatch on the observation format the tree kernels write (obs_dtype 0: f32 planes, 1: f16 planes, 2: f16 NHWC8 rows): CALL sees the
 // element type OBS, the flag NHWC8 and the buffer as OBS *o
@@ -1542,6 +1545,8 @@ extern "C" int azg_launch_support(int game, int channels) {
     if (game < 0 || game >= k_num_games) return fail(AZG_E_INVALID_ARG, "unknown game id");
     // tic-tac-toe is built for 32-channel towers only (both of its nets): any other width is refused, not answered with an empty mask
     if (game == AZG_GAME_TICTACTOE && channels != 32) return fail(AZG_E_UNSUPPORTED, "tic-tac-toe has 32-channel launches only");
+    // hnefatafl has device rules and no tile row: its network runs outside the library
+    if (game == AZG_GAME_HNEFATAFL) return fail(AZG_E_INVALID_ARG, "no network launch is built for this game");
     return tile_support(game, channels);
 }
 

@@ -814,4 +814,283 @@ struct TT {
     }
 };
 
+// ================================================================================================ hnefatafl
+// 11x11 tafl: alphazero/envs/hnefatafl/fastafl.pyx (Game) + fastafl/cengine.pyx (Board), board options of variants.hnefatafl_args: NO
+// two-sided king capture (the king is never taken by custodian capture; Board.king_captured() is recomputed from the board at every
+// get_winner: every in-bounds neighbour of the king holds a defender-code piece 2, the empty throne or a corner), moves over the empty
+// throne, the king cannot re-enter it.  Board codes and the action codec are brandubh's with 11 in place of 7: action = 20 (x + 11 y) +
+// move_type.  121 cells are more than a wavefront has lanes: lane l owns cell l (c0) and cell 64 + l (c1, l < 57), and a set of cells
+// is a 128-bit mask M of two wave ballots, bit c & 63 of word c >> 6 -- the word boundary falls inside row 5, between x = 8 and x = 9.
+// Shifts by one row (11) and one column (1, with the wrapping column cleared first) carry between the words.  Everything else follows
+// struct BR: sliding moves from the 11-bit row of the passable mask and, through the transposed board, its column; custodian captures
+// by uniform reads around the moved piece; the group-surround check (cengine.pyx:204-247) as a flood fill on the masks.
+struct HN {
+    static constexpr int ID = AZG_GAME_HNEFATAFL;
+    static constexpr int A = 2420, H = 11, W = 11, CELLS = 121, P = 2, HAS_DRAW = 1, MAX_TURNS = 512, NSYM = 8;
+    // MAXK bounds the move list of ANY board azg_set_states can hand over: every move lands on a cell that holds no piece, and a cell is
+    // reached by at most one mover piece from each of the four directions, so with n mover pieces k <= min(20 n, 4 (121 - n)) <= 403
+    // (n = 20); 448 = seven chunks of 64.  valid_list clamps all the same.
+    static constexpr int OBS_C = 5, OBS = OBS_C * CELLS, MAXK = 448;
+    static constexpr int SYM_RAW = 6;                                    // the identity, as brandubh (fastafl.pyx:216-259, k = 2*(4-1) + 0)
+    static constexpr int HI = CELLS - 64;                                // cells of the second word
+    struct M { uint64_t lo, hi; };
+    struct S { int c0, c1; int player, turns, kc; };                     // c1 == 0 in lanes >= HI, always
+
+    static constexpr M colmask(int x) {
+        M m{0, 0};
+        for (int y = 0; y < 11; y++) { const int c = 11 * y + x; if (c < 64) m.lo |= 1ULL << c; else m.hi |= 1ULL << (c - 64); }
+        return m;
+    }
+    static constexpr uint64_t HI_ALL = (1ULL << HI) - 1;
+    static AZG_DEV M mor(M a, M b) { return M{a.lo | b.lo, a.hi | b.hi}; }
+    static AZG_DEV M mand(M a, M b) { return M{a.lo & b.lo, a.hi & b.hi}; }
+    static AZG_DEV M mandn(M a, M b) { return M{a.lo & ~b.lo, a.hi & ~b.hi}; }           // a without b
+    static AZG_DEV bool any(M a) { return (a.lo | a.hi) != 0; }
+    static AZG_DEV bool same(M a, M b) { return a.lo == b.lo && a.hi == b.hi; }
+    static AZG_DEV M single(int c) { return c < 64 ? M{1ULL << (c & 63), 0ULL} : M{0ULL, 1ULL << (c & 63)}; }
+    static AZG_DEV bool has(M a, int c) { return (((c < 64 ? a.lo : a.hi) >> (c & 63)) & 1) != 0; }
+    static AZG_DEV M shl(M m, int d) { return M{m.lo << d, (m.hi << d) | (m.lo >> (64 - d))}; }      // 0 < d < 64
+    static AZG_DEV M shr(M m, int d) { return M{(m.lo >> d) | (m.hi << (64 - d)), m.hi >> d}; }
+    static AZG_DEV M nbr(M m) {                     // squares orthogonally adjacent to the set m (board edges: nothing)
+        constexpr M C0 = colmask(0), C10 = colmask(10);
+        const M a = shl(m, 11), b = shr(m, 11), c = shl(mandn(m, C10), 1), d = shr(mandn(m, C0), 1);
+        return M{a.lo | b.lo | c.lo | d.lo, (a.hi | b.hi | c.hi | d.hi) & HI_ALL};
+    }
+    // the 11 bits of m from bit p (p = 11 j, per lane)
+    static AZG_DEV unsigned line11(M m, int p) {
+        const uint64_t v = p < 64 ? ((m.lo >> (p & 63)) | (p ? (m.hi << ((64 - p) & 63)) : 0ULL)) : (m.hi >> ((p - 64) & 63));
+        return (unsigned)v & 0x7FFu;
+    }
+    static AZG_DEV bool is_king(int v) { return v == 3 || v == 7 || v == 8; }
+    static AZG_DEV bool is_att(int v) { return v == 1 || is_king(v); }                       // ATTACKERS cengine.pyx:42
+    template <class F> static AZG_DEV M mask(const S &s, int lane, F &&f) { return M{__ballot(f(s.c0)), __ballot(lane < HI && f(s.c1))}; }
+    static AZG_DEV M mask_eq(const S &s, int lane, int v) { return M{__ballot(s.c0 == v), __ballot(lane < HI && s.c1 == v)}; }
+    // the value of cell idx: a wave-uniform index / a per-lane one (every lane takes part)
+    static AZG_DEV int rd(const S &s, int idx) {
+        idx = __builtin_amdgcn_readfirstlane(idx);
+        const int a = __builtin_amdgcn_readlane(s.c0, idx & 63), b = __builtin_amdgcn_readlane(s.c1, idx & 63);
+        return idx < 64 ? a : b;
+    }
+    static AZG_DEV int get(const S &s, int idx) {
+        const int a = __shfl(s.c0, idx & 63), b = __shfl(s.c1, idx & 63);
+        return idx < 64 ? a : b;
+    }
+    static AZG_DEV void put(S &s, int lane, int idx, int v) {            // idx < CELLS, wave-uniform
+        if (idx < 64) { if (lane == idx) s.c0 = v; } else if (lane == idx - 64) s.c1 = v;
+    }
+
+    static AZG_DEV S load(const azg_state *st, int lane) {               // (azg.h: two cells per byte, the even cell in the low nibble)
+        const uint8_t *q = reinterpret_cast<const uint8_t *>(st->cells);
+        const int c1 = 64 + lane;
+        S s;
+        s.c0 = (q[lane >> 1] >> ((lane & 1) * 4)) & 15;
+        s.c1 = lane < HI ? (q[c1 >> 1] >> ((c1 & 1) * 4)) & 15 : 0;
+        s.player = __builtin_amdgcn_readfirstlane(st->player);
+        s.turns = __builtin_amdgcn_readfirstlane(st->turns);
+        s.kc = __builtin_amdgcn_readfirstlane(st->aux[0]);
+        return s;
+    }
+    static AZG_DEV int start_cell(int c) {          // fastafl/variants.py:1-11: the standard 11x11 opening
+        const int y = c / 11, x = c - y * 11;
+        const int dx = x < 5 ? 5 - x : x - 5, dy = y < 5 ? 5 - y : y - 5;
+        if (dx == 5 && dy == 5) return 5;
+        if (dx == 0 && dy == 0) return 7;
+        if (dx + dy <= 2) return 1;
+        if ((dy == 5 && dx <= 2) || (dx == 5 && dy <= 2) || (dy == 4 && dx == 0) || (dx == 4 && dy == 0)) return 2;
+        return 0;
+    }
+    static AZG_DEV void init(S &s) {
+        const int lane = threadIdx.x & 63;
+        s.c0 = start_cell(lane); s.c1 = lane < HI ? start_cell(64 + lane) : 0;
+        s.player = 0; s.turns = 0; s.kc = 0;
+    }
+    static AZG_DEV void store(const S &s, azg_state *st, int lane) {     // lane j writes byte j: cells 2j and 2j + 1 (cell 121 and bytes 61..63: zero)
+        const int ve = get(s, 2 * lane), vo = get(s, 2 * lane + 1);
+        st->cells[lane] = lane * 2 < CELLS ? (int8_t)(ve | (vo << 4)) : (int8_t)0;
+        if (lane == 0) { st->player = s.player; st->turns = s.turns; st->aux[0] = s.kc; st->aux[1] = 0; }
+    }
+    static AZG_DEV void decode(int a, int &src, int &dst) {          // fastafl.pyx:46-63 get_move
+        const int mt = a % 20; src = a / 20;
+        const int sx = src % 11, sy = src / 11;
+        int nx, ny;
+        if (mt < 10) { nx = sx; ny = mt + (mt >= sy ? 1 : 0); }
+        else { nx = mt - 10; nx += (nx >= sx ? 1 : 0); ny = sy; }
+        dst = ny * 11 + nx;
+    }
+    static AZG_DEV int encode(int x, int y, int nx, int ny) {        // fastafl.pyx:66-79 get_action
+        const int mt = x == nx ? (ny < y ? ny : ny - 1) : (nx < x ? 10 + nx : 10 + nx - 1);
+        return 20 * (x + y * 11) + mt;
+    }
+    // Board.move (cengine.pyx:249-272, no validity / win checks) + _check_capture (:174-199) + _check_surround (:228-247)
+    static AZG_DEV void play(S &s, int a) {
+        const int lane = threadIdx.x & 63;
+        a = __builtin_amdgcn_readfirstlane(a);
+        int src, dst; decode(a, src, dst);
+        const int srcv = rd(s, src), dstv = rd(s, dst);
+        const int piece = (srcv == 7 || srcv == 8) ? 3 : srcv;                               // remove_piece :315-330
+        const int newsrc = srcv == 7 ? 4 : srcv == 8 ? 5 : 0;
+        const int newdst = (dstv == 4 || dstv == 5) ? piece + dstv : piece;                  // add_piece :294-313
+        put(s, lane, src, newsrc);
+        put(s, lane, dst, newdst);
+        // every capture below starts from a square next to the moved piece that holds an enemy (custodian: 3 - mover, never a king;
+        // surround: the enemy team, kings included for a black mover): most moves have none, and are done here
+        {
+            const bool black = newdst == 2;
+            const M relevant = black ? mask(s, lane, [](int v) { return is_att(v); }) : mask_eq(s, lane, 2);
+            if (!any(mand(nbr(single(dst)), relevant))) { s.turns += 1; s.player ^= 1; return; }
+        }
+        const int dx4[4] = {0, 1, 0, -1}, dy4[4] = {1, 0, -1, 0};                            // DIRECTIONS :46
+        const int mx = dst % 11, my = dst / 11;
+        // ---- custodian capture around the moved piece: against a friendly piece, the empty throne or a corner ----
+        const bool friendly_att = is_att(newdst);
+        const int enemy = newdst != 3 ? 3 - newdst : 2;
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            const int ex = mx + dx4[d], ey = my + dy4[d];
+            if (ex < 0 || ex > 10 || ey < 0 || ey > 10) continue;
+            if (rd(s, ey * 11 + ex) != enemy) continue;
+            const int fx = ex + dx4[d], fy = ey + dy4[d];
+            if (fx < 0 || fx > 10 || fy < 0 || fy > 10) continue;
+            const int fv = rd(s, fy * 11 + fx);
+            const bool friendly = friendly_att ? is_att(fv) : fv == newdst;
+            if (friendly || fv == 4 || fv == 5) put(s, lane, ey * 11 + ex, 0);
+        }
+        // ---- group surround: start squares in DIRECTIONS order, removals visible to the later ones ----
+        const bool enemy_is_att = rd(s, dst) == 2;
+        M checked{0, 0};
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            const int ex = mx + dx4[d], ey = my + dy4[d];
+            if (ex < 0 || ex > 10 || ey < 0 || ey > 10) continue;
+            const int e = ey * 11 + ex;
+            const M enemyM = enemy_is_att ? mask(s, lane, [](int v) { return is_att(v); }) : mask_eq(s, lane, 2);
+            if (!has(enemyM, e) || has(checked, e)) continue;
+            M g = single(e);
+            for (;;) { const M g2 = mor(g, mand(nbr(g), enemyM)); if (same(g2, g)) break; g = g2; }
+            checked = mor(checked, g);
+            if (!any(mand(nbr(g), mask_eq(s, lane, 0)))) {                                   // every member fully blocked
+                if (any(mand(g, mask(s, lane, [](int v) { return is_king(v); })))) s.kc = 1; // a king is never lifted (:242-243)
+                if (((g.lo >> lane) & 1) && !is_king(s.c0)) s.c0 = 0;
+                if (lane < HI && ((g.hi >> lane) & 1) && !is_king(s.c1)) s.c1 = 0;
+            }
+        }
+        s.turns += 1; s.player ^= 1;
+    }
+    // Game.win_state (fastafl.pyx:194-206: the draw first) + Board.get_winner (cengine.pyx:163-169) + king_captured (:154-161) +
+    // _has_legals_check (:134-141)
+    static AZG_DEV int win_bits(const S &s) {
+        const int lane = threadIdx.x & 63;
+        if (s.turns >= MAX_TURNS) return 4;
+        const M esc = mask_eq(s, lane, 8), m2 = mask_eq(s, lane, 2);
+        const M adjE = nbr(mask_eq(s, lane, 0)), adjX = nbr(mask_eq(s, lane, 5));
+        const M kings = mask(s, lane, [](int v) { return is_king(v); });
+        const bool def_has = any(mand(m2, adjE));
+        const bool att_has = any(mor(mand(mask_eq(s, lane, 1), adjE), mand(kings, mor(adjE, adjX))));
+        if (any(esc) || !def_has) return 2;           // attackers (player 1) win: result[2 - 1]
+        // a king all of whose in-bounds neighbours hold 2, the empty throne or a corner (KING_CAPTURE :44)
+        const M holds = mask(s, lane, [](int v) { return v == 2 || v == 4 || v == 5; });
+        const M open = M{~holds.lo, ~holds.hi & HI_ALL};
+        const bool boxed = any(mandn(kings, nbr(open)));
+        if (s.kc || boxed || !att_has) return 1;      // defenders (player 0) win: result[2 - 2]
+        return 0;
+    }
+    // cells of an 11-cell line (bit p = the piece's own position) a sliding piece at p reaches: the runs of passable cells on both
+    // sides of p (Board.legal_moves walks them square by square, cengine.pyx:109-132)
+    static AZG_DEV unsigned reach11(unsigned line, int p) {
+        const unsigned up = line >> (p + 1);                                  // cells above p, bit 0 = p + 1
+        const unsigned run = (unsigned)__builtin_ctz(~up);                    // trailing ones (an 11-bit line: ~up is never 0)
+        const unsigned reach_up = ((1u << run) - 1u) << (p + 1);
+        const unsigned below = (1u << p) - 1u, blk = ~line & below;           // blockers below p
+        const unsigned cut = blk ? (2u << (31 - __builtin_clz(blk))) : 1u;    // first bit above the highest blocker
+        return reach_up | (line & below & ~(cut - 1u));
+    }
+    // the 20 move types of the piece on cell c (< CELLS) as a bit set: vertical ny -> ny or ny - 1, horizontal nx -> 10 + nx or 10 + nx - 1
+    // (fastafl.pyx:66-79).  pass / passT: the cells a ray continues over, T / Tt the empty throne (nobody lands on it), both also transposed
+    static AZG_DEV unsigned cell_moves(M pass, M passT, M T, M Tt, int c) {
+        const int y = c / 11, x = c - y * 11;
+        const unsigned row = line11(pass, 11 * y), col = line11(passT, 11 * x);
+        const unsigned rx = reach11(row, x) & ~line11(T, 11 * y), ry = reach11(col, y) & ~line11(Tt, 11 * x);
+        const unsigned mvy = (ry & ((1u << y) - 1u)) | ((ry >> (y + 1)) << y), mvx = (rx & ((1u << x) - 1u)) | ((rx >> (x + 1)) << x);
+        return mvy | (mvx << 10);
+    }
+    // Game.valid_moves (fastafl.pyx:179-186) + Board.legal_moves (cengine.pyx:109-132): ascending action list in LDS -- cells in
+    // ascending order (the lanes' first cells, then their second ones), the move types of a cell in ascending order.
+    static AZG_DEV int valid_list(const S &s, int lane, int *act_lds, int (&my_a)[7]) {
+        const int team = 2 - (s.turns & 1);                                                  // Board.to_play :332-333
+        const int cA = lane, cB = lane < HI ? 64 + lane : CELLS - 1;
+        const bool mineA = team == 1 ? is_att(s.c0) : s.c0 == 2, mineB = lane < HI && (team == 1 ? is_att(s.c1) : s.c1 == 2);
+        // the transposed board: the cell (x, y) of the lane's cell (y, x)
+        const int tA = get(s, (cA % 11) * 11 + cA / 11), tB = get(s, (cB % 11) * 11 + cB / 11);
+        const M E = mask_eq(s, lane, 0), T = mask_eq(s, lane, 4), X = mask_eq(s, lane, 5);
+        const M Et{__ballot(tA == 0), __ballot(lane < HI && tB == 0)}, Tt{__ballot(tA == 4), __ballot(lane < HI && tB == 4)},
+                Xt{__ballot(tA == 5), __ballot(lane < HI && tB == 5)};
+        const M ET = mor(E, T), ETt = mor(Et, Tt), ETX = mor(ET, X), ETXt = mor(ETt, Xt);    // (only the king's ray enters a corner)
+        const bool kA = is_king(s.c0), kB = is_king(s.c1);
+        const unsigned mvA = mineA ? cell_moves(kA ? ETX : ET, kA ? ETXt : ETt, T, Tt, cA) : 0u;
+        const unsigned mvB = mineB ? cell_moves(kB ? ETX : ET, kB ? ETXt : ETt, T, Tt, cB) : 0u;
+        const int cntA = __popc(mvA), cntB = __popc(mvB);
+        const int totA = wave_sum_i(cntA), k = totA + wave_sum_i(cntB);
+        const int offA = wave_excl_scan(cntA, lane), offB = totA + wave_excl_scan(cntB, lane);
+        wave_sync();                                                     // (an earlier list's reads are done)
+#pragma unroll
+        for (int b = 0; b < 20; b++) {
+            const int pa = offA + __popc(mvA & ((1u << b) - 1u)), pb = offB + __popc(mvB & ((1u << b) - 1u));
+            if (((mvA >> b) & 1u) && pa < MAXK) act_lds[pa] = 20 * cA + b;
+            if (((mvB >> b) & 1u) && pb < MAXK) act_lds[pb] = 20 * cB + b;
+        }
+        wave_sync();
+        const int kk = k < MAXK ? k : MAXK;
+#pragma unroll
+        for (int c = 0; c < 7; c++) my_a[c] = c * 64 + lane < kk ? act_lds[c * 64 + lane] : -1;
+        wave_sync();
+        return kk;
+    }
+    // Game.observation (fastafl.pyx:82-119,208-214): planes [black(2), white(1), king, to-move colour, turns / 512 in integers]
+    static AZG_DEV float plane(int p, int c, const S &s) {
+        return p == 0 ? (c == 2 ? 1.f : 0.f) : p == 1 ? (c == 1 ? 1.f : 0.f) : p == 2 ? (is_king(c) ? 1.f : 0.f)
+             : p == 3 ? (float)(s.turns & 1) : (float)(s.turns / MAX_TURNS);
+    }
+    template <typename OT_> static AZG_DEV void write_obs(const S &s, OT_ *out, int lane) {
+#pragma unroll
+        for (int p = 0; p < OBS_C; p++) {
+            out[p * CELLS + lane] = (OT_)plane(p, s.c0, s);
+            if (lane < HI) out[p * CELLS + 64 + lane] = (OT_)plane(p, s.c1, s);
+        }
+    }
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    static AZG_DEV h8 obs8(const S &s, int c) {                  // the five planes of cell c, one of the calling lane's OWN two cells (lane or 64 + lane)
+        const int v = c < 64 ? s.c0 : s.c1;
+        return (h8){(_Float16)plane(0, v, s), (_Float16)plane(1, v, s), (_Float16)plane(2, v, s), (_Float16)plane(3, v, s),
+                    (_Float16)plane(4, v, s), (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+    }
+    static AZG_DEV void write_obs_nhwc8(const S &s, _Float16 *out, int lane) {
+        *reinterpret_cast<h8 *>(out + lane * 8) = obs8(s, lane);
+        if (lane < HI) *reinterpret_cast<h8 *>(out + (64 + lane) * 8) = obs8(s, 64 + lane);
+    }
+    // Game.symmetries (fastafl.pyx:216-259): k = (i-1)*2 + flip; state = fliplr^flip(rot90^i(state)); the policy index is permuted by
+    // the reference's own coordinate loop (sym_action)
+    static AZG_DEV int sym_source(int c, int i, int flip) {
+        int r = c / 11, cc = c - (c / 11) * 11;
+        if (flip) cc = 10 - cc;                            // final[r][c] = rotated[r][10-c]
+        for (int t = 0; t < i; t++) { const int nr = cc, nc = 10 - r; r = nr; cc = nc; }    // rot90: new[r][c] = old[c][10-r]
+        return r * 11 + cc;
+    }
+    static AZG_DEV S symmetry(const S &s, int k) {
+        const int lane = threadIdx.x & 63;
+        const int i = k / 2 + 1, flip = k & 1;
+        S o = s;
+        const int v0 = get(s, sym_source(lane, i, flip)), v1 = get(s, sym_source(lane < HI ? 64 + lane : 0, i, flip));
+        o.c0 = v0; o.c1 = lane < HI ? v1 : 0;
+        return o;
+    }
+    static AZG_DEV int sym_action(int a, int k) {
+        const int i = k / 2 + 1, flip = k & 1;
+        int src, dst; decode(a, src, dst);
+        int x = src % 11, y = src / 11, nx = dst % 11, ny = dst / 11;
+        for (int t = 0; t < i; t++) { const int tx = x, tnx = nx; x = 10 - y; nx = 10 - ny; y = tx; ny = tnx; }   // :241-247
+        if (flip) { x = 10 - x; nx = 10 - nx; }
+        return encode(x, y, nx, ny);
+    }
+};
+
 }  // namespace azg

@@ -98,7 +98,7 @@ namespace azg {
 // sparse heads (head features -> logits of the leaf's children only) are not built for gobang, where nearly every cell is a legal
 // move: a sparse row saves little and the 3616-wide feature dot products would spill
 // nor for tic-tac-toe: A = 9 is one output subtile, which the exact heads compute whole at the same cost
-template <class G> constexpr bool has_sparse_heads = G::ID != AZG_GAME_GOBANG && G::ID != AZG_GAME_TICTACTOE;
+template <class G> constexpr bool has_sparse_heads = G::ID != AZG_GAME_GOBANG && G::ID != AZG_GAME_TICTACTOE && G::ID != AZG_GAME_HNEFATAFL;
 
 // azg_launch_support: the AZG_SUPPORT_* mask of (game, tower width); 0 for a game id the lists do not know
 inline int tile_support(int game, int channels) {

@@ -49,7 +49,9 @@ typedef enum azg_game {
     AZG_GAME_TRIMOK = 2,        /* build-defined 3-player env (N-player path, BASELINE config 5)     */
     AZG_GAME_OTHELLO = 3,       /* alphazero/envs/othello/othello.pyx + OthelloLogic.pyx (ABI v7)    */
     AZG_GAME_GOBANG = 4,        /* alphazero/envs/gobang/gobang.pyx + GobangLogic.pyx (ABI v7)       */
-    AZG_GAME_TICTACTOE = 5      /* alphazero/envs/tictactoe/tictactoe.py + TicTacToeLogic.py (ABI v7) */
+    AZG_GAME_TICTACTOE = 5,     /* alphazero/envs/tictactoe/tictactoe.py + TicTacToeLogic.py (ABI v7) */
+    AZG_GAME_HNEFATAFL = 6      /* alphazero/envs/hnefatafl/fastafl.pyx + fastafl/cengine.pyx, variants.hnefatafl_args (ABI v7):
+                                   device rules and every tree / raw-search launch; NO network launch (azg_launch_support) */
 } azg_game;
 
 /* Game state as it crosses the ABI (all games): the reference's board array, row-major, one int8 per cell
@@ -61,7 +63,12 @@ typedef enum azg_game {
  * (action a = 15x + y) is bit 16x + y, bit 15 of every row and bits 240..255 are zero.  aux is zero.  The Python layer
  * (engine.py) packs and unpacks, so its callers still see 225 int8 cells.
  * Tic-tac-toe: cells[3x + y] = pieces[x][y] of TicTacToeLogic.py (1 = player 0's colour, -1 = player 1's, 0 = empty), cells 9..63 and
- * aux zero; action a plays cell a.  Any assignment of the nine cells is accepted, reachable or not. */
+ * aux zero; action a plays cell a.  Any assignment of the nine cells is accepted, reachable or not.
+ * Hnefatafl's 11x11 board (121 cells, piece codes of fastafl/cengine.pyx:24-32 as brandubh, all below 16) packs two cells per byte: cell
+ * c = 11y + x is the low nibble of byte c / 2 for even c, the high nibble for odd c; bytes 61..63 are zero.  aux[0] =
+ * Board._king_captured (set by the group-surround check only), aux[1] = 0.  The Python layer (engine.py) packs and unpacks, so its
+ * callers see 121 int8 cells.  max_children = 448 bounds the move list of any board: a move lands on a cell without a piece and a cell
+ * is reached by at most one mover piece per direction, so k <= min(20 n, 4 (121 - n)) <= 403 for n mover pieces. */
 typedef struct azg_state {
     int8_t  cells[64];
     int32_t player;
@@ -398,7 +405,9 @@ int  azg_tower_layout(int game, int boards_per_tile, int channels, int16_t *pixm
 
 /* Which network launches are instantiated for (game, tower width): a mask of AZG_SUPPORT_* bits, from the same tile lists the launches
  * are built from (csrc/azg_tiles.h; no device needed).  AZG_E_INVALID_ARG for an unknown game; AZG_E_UNSUPPORTED for tic-tac-toe at
- * any width but 32, the only one that game is built for. */
+ * any width but 32, the only one that game is built for.  Hnefatafl (game 6) has device rules but no tile row: the answer stays
+ * AZG_E_INVALID_ARG ("no network launch is built for this game") at every width, and its network runs outside the library
+ * (azg_select / the caller's network / azg_backup, or azg_backup_select). */
 int  azg_launch_support(int game, int channels);
 #define AZG_SUPPORT_TOWER         1   /* the stand-alone MFMA tower: azg_resnet_tower_f16 / azg_resnet_tower_features_f16              */
 #define AZG_SUPPORT_SEARCH_WIDE   2   /* factorised heads, exact: azg_search_wide_exact_f16 and azg_search_arena_wide_exact_f16        */

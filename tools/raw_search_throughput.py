@@ -6,6 +6,9 @@ runs on a commit that has no such launch (it then measures only the forms that c
   (b) ms per warm-up round of SelfPlayRunner(warmup=True, numWarmupSims=5) at 128 / 512 / 2048 slots, connect4 and brandubh: graph replay
       of the launch-per-phase form and of the raw launch, alternating, `--reps` times `--rounds` rounds each; median with min / max.
   (c) tree-only expansions/s of the raw launch itself at 2048 connect4 slots x 100 simulations per move (no network anywhere).
+  (d) `--hnefatafl`: 128 / 512 / 2048 hnefatafl games x 100 simulations per move (the widest move lists: up to seven chunks of 64
+      children), the raw launch against `sims` x [azg_select(NULL), azg_backup] of the same build, alternating: expansions/s and ms per
+      move, median of `--reps` repetitions with the spread.  Written to profiles/hnefatafl_raw_throughput.json.  A record, not a bar.
 
 Every timed window ends in a device synchronise.  One JSON line per case; all of them go to `--out` under `--label` (the file keeps the
 other labels it holds: run it on the commit before and on this one, profiles/raw_search_throughput.json holds both)."""
@@ -125,6 +128,49 @@ def tree_only(B, sims, moves, reps):
     return dict(case='tree_only', game='connect4', slots=B, sims=sims, moves=moves, reps=reps, form='launch', expansions_per_s=med(rates))
 
 
+def hnefatafl_moves(B, sims, moves, reps):
+    """(d): whole moves (`sims` simulations + playMoves, no samples kept) of B hnefatafl games from the opening, the two forms alternating"""
+    Game = game_cls('hnefatafl')
+    gid = Game.AZG_GAME_ID
+    # (the library's default store holds 16 moves' worth of 448-child expansions: 46 MB a tree; three moves' worth is plenty here -- a
+    #  move adds about sims x 120 nodes and the played child's subtree is compacted once less than a move's worth is free)
+    mk = lambda: DeviceEngine(gid, B, seed=3, sims_hint=sims, add_root_noise=True, add_root_temp=True, nodes_per_tree=3 * sims * 448 + 64)
+    eng = dict(launch=mk(), phase=mk())
+    fill, vrow = float(np.float32(1 / eng['phase'].A)), np.full(eng['phase'].NV, 1 / eng['phase'].NV, np.float32)
+    pol = torch.full((B, eng['phase'].A), fill, dtype=torch.float32, device=eng['phase'].device)
+    val = torch.from_numpy(np.tile(vrow, (B, 1))).to(eng['phase'].device)
+
+    def move(f):
+        e = eng[f]
+        if f == 'launch':
+            e.search_raw(sims, fill, vrow)
+        else:
+            for _ in range(sims):
+                e.select(None)
+                e.backup(pol, val)
+        e.advance(False)
+    ms, rate = {f: [] for f in eng}, {f: [] for f in eng}
+    for f in eng:
+        move(f)
+    for _ in range(reps):
+        for f in eng:
+            torch.cuda.synchronize()
+            x0 = eng[f].counters()['expansions']
+            t0 = time.perf_counter()
+            for _ in range(moves):
+                move(f)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            ms[f].append(dt * 1e3 / moves)
+            rate[f].append((eng[f].counters()['expansions'] - x0) / dt)
+    same = bool(torch.equal(eng['launch'].root_counts(), eng['phase'].root_counts()))
+    out = [dict(case='hnefatafl_move', game='hnefatafl', slots=B, sims=sims, moves=moves, reps=reps, form=f, ms_per_move=med(ms[f]),
+                expansions_per_s=med(rate[f]), max_nodes_used=eng[f].counters()['max_nodes_used'], forms_agree=same) for f in eng]
+    for e in eng.values():
+        e.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--label', required=True, help="which commit this is, e.g. 'parent' or 'branch'")
@@ -134,6 +180,7 @@ def main():
     ap.add_argument('--moves', type=int, default=8)
     ap.add_argument('--rounds', type=int, default=30)
     ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--hnefatafl', action='store_true', help='case (d) only, into profiles/hnefatafl_raw_throughput.json')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'a measurement needs the GPU'
     rows = []
@@ -141,13 +188,20 @@ def main():
     def emit(r):
         print(json.dumps(r), flush=True)
         rows.append(r)
+    if a.hnefatafl:
+        if a.out == ap.get_default('out'):
+            a.out = os.path.join(ROOT, 'profiles', 'hnefatafl_raw_throughput.json')
+        for B in a.slots:
+            for r in hnefatafl_moves(B, 100, a.moves, a.reps):
+                emit(r)
+        a.games = []
     for g in a.games:
         emit(raw_search_moves(g, a.moves, a.reps))
     for g in a.games:
         for B in a.slots:
             for r in warmup_rounds(g, B, a.rounds, a.reps):
                 emit(r)
-    if HAS_RAW:
+    if HAS_RAW and not a.hnefatafl:
         emit(tree_only(2048, 100, 10, a.reps))
     doc = {}
     if os.path.exists(a.out):
