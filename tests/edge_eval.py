@@ -91,8 +91,8 @@ def agent_row(seed, stream, step, A, NV):
 
 # ---- replay helpers (the oracle's rules, the host envs' for othello and gobang; used by the CPU and GPU replays of the edge fixtures) ----
 CONFIGS = ['uniform_q', 'uniform_bonus', 'dyadic', 'dyadic_noise1', 'onehot', 'onehot_q', 'spread', 'spread_powf']
-GAMES = {'c4': 0, 'br': 1, 'tm': 2, 'ot': 3, 'gb': 4, 'gbr': 4}
-HOST_GAMES = (3, 4)                                          # no C oracle: replayed on alphazero_general_amd.envs.{othello,gobang}
+GAMES = {'c4': 0, 'br': 1, 'tm': 2, 'ot': 3, 'gb': 4, 'gbr': 4, 'tt': 5}
+HOST_GAMES = (3, 4, 5)                                       # no C oracle: replayed on alphazero_general_amd.envs.{othello,gobang,tictactoe}
 
 
 def game_sizes(gid):
@@ -106,8 +106,8 @@ def game_sizes(gid):
 
 
 def host_game(gid):
-    from alphazero_general_amd.envs import gobang, othello
-    return {3: othello.Game, 4: gobang.Game}[gid]
+    from alphazero_general_amd.envs import gobang, othello, tictactoe
+    return {3: othello.Game, 4: gobang.Game, 5: tictactoe.Game}[gid]
 
 
 def roots(d, gid):

@@ -11,6 +11,7 @@ probabilities do not depend on its batch position (tests/test_gpu_nnet.py), so t
 import numpy as np
 import pytest
 
+import fixture_checks as FC
 import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
@@ -68,12 +69,9 @@ def test_search_launch_equals_phase_launches_at_2048x100():
             eb.select(obs)
             p, v = hip.forward_nhwc8(obs)
             eb.backup(p, v)
-        assert torch.equal(ea.root_counts(), eb.root_counts())
-        assert torch.equal(ea.root_probs(1.0), eb.root_probs(1.0))
-        assert torch.equal(ea.root_value(False), eb.root_value(False))
+        FC.assert_engines_equal(ea, eb, ('counts', 'probs', 'vmax'), n)     # (the comparisons of this size as they were: named, not widened)
         ea.advance(True); eb.advance(True)
-        assert torch.equal(ea.last_actions(), eb.last_actions())
-        assert (ea.tape_counters() == eb.tape_counters()).all()
+        FC.assert_engines_equal(ea, eb, ('actions', 'tapes'), n)
 
     for _ in range(4):
         move(sims)
@@ -81,12 +79,9 @@ def test_search_launch_equals_phase_launches_at_2048x100():
         move(9)
     for _ in range(3):
         move(sims)
-    a, b = ea.counters(), eb.counters()
-    assert a == b and a['sims'] == B * (7 * sims + 12 * 9) and a['games_played'] > 0
-    for x, y in zip(ea.examples(), eb.examples()):
-        assert x.shape[0] > 0 and torch.equal(x, y)
-    for x, y in zip(ea.results(), eb.results()):
-        assert (x == y).all()
+    FC.assert_engines_equal(ea, eb, ('counters', 'examples', 'results'))
+    a = ea.counters()
+    assert a['sims'] == B * (7 * sims + 12 * 9) and a['games_played'] > 0 and all(x.shape[0] > 0 for x in ea.examples())
 
 
 def test_arena_256x100_graph_equals_host_split():
@@ -383,16 +378,11 @@ def test_wide_search_launch_equals_phase_launches(game, B, sims):
         eb.select(obs)
         for s in range(sims):
             eb.backup_select_features(hip.forward_features_nhwc8(obs), hip.head_rows, hip.head2_b, obs, select=s + 1 < sims)
-        assert torch.equal(ea.root_counts(), eb.root_counts()), move
-        assert torch.equal(ea.root_probs(1.0), eb.root_probs(1.0))
-        assert torch.equal(ea.root_value(True), eb.root_value(True))
+        FC.assert_engines_equal(ea, eb, ('counts', 'probs', 'vavg'), move)  # (the comparisons of this test as they were: named, not widened)
         ea.advance(True); eb.advance(True)
-        assert torch.equal(ea.last_actions(), eb.last_actions())
-        assert (ea.tape_counters() == eb.tape_counters()).all()
-    a, b = ea.counters(), eb.counters()
-    assert a == b and a['sims'] == B * sims * moves
-    for x, y in zip(ea.examples(), eb.examples()):
-        assert torch.equal(x, y)
+        FC.assert_engines_equal(ea, eb, ('actions', 'tapes'), move)
+    FC.assert_engines_equal(ea, eb, ('counters', 'examples'))
+    assert ea.counters()['sims'] == B * sims * moves
 
 
 @pytest.mark.parametrize('game,B,sims', [('brandubh', 203, 23), ('trimok', 131, 17), ('brandubh', 512, 200), ('brandubh', 1, 2), ('trimok', 3, 2),
@@ -429,16 +419,11 @@ def test_wide_exact_search_launch_equals_logits_phase_launches(game, B, sims):
         eb.select(obs)
         for s in range(sims):
             eb.backup_select_logits(hip.forward_logits_nhwc8(obs), obs, select=s + 1 < sims)
-        assert torch.equal(ea.root_counts(), eb.root_counts()), move
-        assert torch.equal(ea.root_probs(1.0), eb.root_probs(1.0))
-        assert torch.equal(ea.root_value(True), eb.root_value(True))
+        FC.assert_engines_equal(ea, eb, ('counts', 'probs', 'vavg'), move)  # (the comparisons of this test as they were: named, not widened)
         ea.advance(True); eb.advance(True)
-        assert torch.equal(ea.last_actions(), eb.last_actions())
-        assert (ea.tape_counters() == eb.tape_counters()).all()
-    a, b = ea.counters(), eb.counters()
-    assert a == b and a['sims'] == B * sims * moves
-    for x, y in zip(ea.examples(), eb.examples()):
-        assert torch.equal(x, y)
+        FC.assert_engines_equal(ea, eb, ('actions', 'tapes'), move)
+    FC.assert_engines_equal(ea, eb, ('counters', 'examples'))
+    assert ea.counters()['sims'] == B * sims * moves
 
 
 def test_wide_search_tiles_with_a_deeper_tower():
@@ -469,10 +454,10 @@ def test_wide_search_tiles_with_a_deeper_tower():
                     eb.backup_select_logits(hip.forward_logits_nhwc8(obs), obs, select=s + 1 < sims)
                 else:
                     eb.backup_select_features(hip.forward_features_nhwc8(obs), hip.head_rows, hip.head2_b, obs, select=s + 1 < sims)
-            assert torch.equal(ea.root_counts(), eb.root_counts()), (exact, move)
+            FC.assert_engines_equal(ea, eb, ('counts',), exact, move)        # (what is new here is the tile: counts, moves and counters)
             ea.advance(True); eb.advance(True)
-            assert torch.equal(ea.last_actions(), eb.last_actions())
-        assert ea.counters() == eb.counters()
+            FC.assert_engines_equal(ea, eb, ('actions',), exact, move)
+        FC.assert_engines_equal(ea, eb, ('counters',), exact)
         ea.close(); eb.close()
 
 

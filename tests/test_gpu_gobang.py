@@ -11,16 +11,16 @@ against the fp64 reference of tests/net_reference.py:
   * the tower, head features, logits and probabilities of the 32-, 64- and 128-channel nets, every border class, depths 0 to 6;
   * NNetWrapper.process on the HIP tower driving the per-phase search; the persistent and sparse-head launches refuse gobang."""
 import os
-import zlib
 
 import numpy as np
 import pytest
 import torch
 
+import fixture_checks as FC
 import net_reference as R
-import oracle_lib as ol
 import test_gpu_net_fp64 as F
 import test_gpu_parity as P
+from fixture_checks import crc
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
@@ -29,25 +29,9 @@ NETS = {'gobang_32x4': ('DEFAULT_NET_ARGS', {}), 'gobang_64x4': ('DEFAULT_NET_AR
         'gobang_128x8': ('GOBANG_NET_ARGS', {})}
 
 
-def crc(a):
-    return zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
-
-
 def _game():
     from alphazero_general_amd.envs.gobang import Game
     return Game
-
-
-def _states(prefix):
-    Game = _game()
-    out = []
-    for row in prefix:
-        g = Game()
-        for a in row:
-            if a >= 0:
-                g.play_action(int(a))
-        out.append(g.to_azg_state())
-    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------------- rules
@@ -102,47 +86,9 @@ def test_gb_rules_vs_reference_tables():
 @pytest.mark.parametrize('fixture,cname', [('gb_tree', 'default'), ('gb_tree', 'cpuct4'), ('gb_tree', 'temp'), ('gb_noise_tree', 'noise_temp')])
 def test_gb_tree_vs_reference_goldens(fixture, cname):
     """gb_noise_tree: root noise over 225 children (four chunks), the reference run with its float32 underflow trap off"""
-    d = dict(np.load(os.path.join(G, fixture + '.npz')))
-    cpuct, fpu, noise, temp, sims = d[cname + '_cfg']
-    noise, temp, sims = bool(noise), bool(temp), int(sims)
-    seed = int(d[cname + '_seed'])
-    R_ = d['prefix'].shape[0]
-    exact = not temp
-    eng = P.engine(game=GB, B=R_, cpuct=cpuct, fpu_reduction=fpu, add_root_noise=noise, add_root_temp=temp, seed=seed, sims_hint=sims)
-    eng.set_states(_states(d['prefix']))
-    obs = eng.new_obs()
-    for s in range(sims):
-        eng.select(obs)
-        for r in range(R_):
-            path = eng.last_path(r)
-            assert len(path) == d[cname + '_depth'][r, s]
-            assert (path[:24] == d[cname + '_paths'][r, s][:len(path)]).all(), (r, s)
-        pol, val = P.fake_batch(torch, seed, range(R_), s, A, NV, eng.device)
-        eng.backup(pol, val)
-        assert (eng.root_counts().cpu().numpy() == d[cname + '_rootn'][:, s]).all(), s
-    kmax = d[cname + '_a'].shape[1]                           # (the fixture keeps the first 128 children of a root in list order)
-    for r in range(R_):
-        ch = eng.root_children(r)
-        k = len(ch['a'])
-        assert k > 64
-        kk = min(k, kmax)
-        assert (ch['a'][:kk] == d[cname + '_a'][r][:kk]).all() and (d[cname + '_a'][r][kk:] == -1).all()
-        assert (ch['n'][:kk] == d[cname + '_n'][r][:kk]).all()
-        for f in ('q', 'p', 'v'):
-            if exact:
-                assert (ch[f][:kk] == d[cname + '_' + f][r][:kk]).all(), (f, r)
-            else:
-                assert np.allclose(ch[f][:kk], d[cname + '_' + f][r][:kk], atol=1e-5), (f, r)
-        info = eng.tree_info(r)
-        assert info['n'] == d[cname + '_root_n'][r] and info['max_depth'] == d[cname + '_maxdepth'][r]
-    assert (eng.root_counts().cpu().numpy() == d[cname + '_counts']).all()
-    assert (eng.root_probs(1.0).cpu().numpy() == d[cname + '_probs'][:, 0]).all()
-    assert (eng.root_probs(0.0).cpu().numpy() == d[cname + '_probs'][:, 4]).all()
-    assert (eng.root_value(False).cpu().numpy() == d[cname + '_vmax']).all()
-    assert (eng.root_value(True).cpu().numpy() == d[cname + '_vavg']).all()
-    assert (eng.tape_counters() == d[cname + '_ctr']).all()
-    eng.counters()
-    eng.close()
+    d = FC.load(fixture)
+    traces = FC.check_tree(GB, d, cname, FC.states_from_prefix(_game(), d['prefix']), FC.TREE, 'gb')
+    assert all(len(a) > 64 for t in traces for a in t['a'])  # (the fixture keeps the first 128 children of a root in list order)
 
 
 AGENT = {'plain': (dict(), dict()),
@@ -153,44 +99,14 @@ AGENT = {'plain': (dict(), dict()),
 @pytest.mark.parametrize('launch', P.LAUNCHES)
 @pytest.mark.parametrize('cname', list(AGENT))
 def test_gb_agent_vs_reference_goldens(cname, launch):
-    d = dict(np.load(os.path.join(G, 'gb_agent.npz')))
-    B, sims, games = int(d[cname + '_B']), int(d[cname + '_sims']), int(d[cname + '_games'])
-    seed, slot_base = int(d[cname + '_seed']), int(d[cname + '_slot_base'])
     kw, rnd = AGENT[cname]
-    eng = P.engine(game=GB, B=B, seed=seed, slot_base=slot_base, games_per_iteration=games, example_capacity=8192, sims_hint=sims, **kw)
-    rec = P.run_engine_agent(torch, eng, seed, slot_base, sims, games, launch=launch, **rnd)
-    assert (np.array(rec['sims']) == d[cname + '_round_sims']).all()
-    assert (np.array(rec['counts']) == d[cname + '_counts']).all()
-    assert (np.array(rec['actions']) == d[cname + '_actions']).all()
-    assert (np.array(rec['games_played']) == d[cname + '_games_played']).all()
-    assert (np.array(rec['obs_crc'], np.uint32) == d[cname + '_obs_crc']).all()
-    obs, pi, z = [t.cpu().numpy() for t in eng.examples()]
-    assert obs.shape == d[cname + '_s_obs'].shape
-    assert (obs == d[cname + '_s_obs']).all() and (pi == d[cname + '_s_pi']).all() and (z == d[cname + '_s_z']).all()
-    ws, turns, _ = eng.results()
-    assert (ws == d[cname + '_r_ws']).all() and (turns == d[cname + '_r_turns']).all()
-    eng.close()
+    FC.check_agent(GB, FC.load('gb_agent'), cname + '_', launch, 'gb', engine_kw=dict(kw, example_capacity=8192), **rnd)
 
 
 def test_gb_mcts_class_api_vs_reference_goldens():
     """alphazero_general_amd.MCTS on an envs.gobang.Game object (one slot: the tape stream of gb_tree's root 0), find_leaf /
     process_results fed the fixture's evaluations, must build the reference's tree: depths, counts, values, probabilities"""
-    from alphazero_general_amd.MCTS import MCTS
-    from alphazero_general_amd.utils import dotdict
-    d = dict(np.load(os.path.join(G, 'gb_tree.npz')))
-    cpuct, fpu, _, _, sims = d['default_cfg']
-    seed, sims = int(d['default_seed']), int(sims)
-    g = _game().from_azg_state(*_states(d['prefix'][:1])[0])
-    m = MCTS(dotdict(cpuct=float(cpuct), fpu_reduction=float(fpu), root_noise_frac=0.1, root_policy_temp=1.1, min_discount=1,
-                     _num_players=3, numMCTSSims=sims, _azg_seed=seed))
-    for s in range(sims):
-        leaf = m.find_leaf(g)
-        assert m.depth == d['default_depth'][0, s]
-        p, v = ol.fake_eval(seed, 0, s, A, NV)
-        m.process_results(leaf, v, p, False, False)
-    assert (np.asarray(m.counts(g)) == d['default_counts'][0]).all()
-    assert m.value(False) == d['default_vmax'][0] and m.value(True) == d['default_vavg'][0]
-    assert (np.asarray(m.probs(g, 1.0), np.float32) == d['default_probs'][0, 0]).all()
+    FC.check_mcts_class(_game(), FC.load('gb_tree'), A, NV, game='gb')
 
 
 # ------------------------------------------------------------------------------------------------------------------------- network
@@ -304,35 +220,13 @@ def test_gb_phase_search_on_the_hip_tower(key):
 def test_gb_wide_exact_search_vs_phase_loop(key, B, sims, moves):
     """azg_search_wide_exact_f16 (one game per workgroup; 227-level paths through the game-sized walk mailbox) against select ->
     NNetWrapper.process -> backup on a twin engine with the same seeds: counts, probabilities, values, moves, samples, results"""
-    from alphazero_general_amd.engine import DeviceEngine
     net = _net(key)
-    kw = dict(cpuct=4.0, fpu_reduction=0.4, add_root_noise=True, add_root_temp=True, seed=41, games_per_iteration=1 << 30,
-              example_capacity=B * (moves + 1) * 8, sims_hint=sims)
-    ea, ec = DeviceEngine(GB, B, **kw), DeviceEngine(GB, B, **kw)
-    oc = ec.new_obs(torch.float32)
-    for mv in range(moves):
-        net._hip.search(ea, sims, exact=True)
-        for _ in range(sims):
-            ec.select(oc)
-            p, v = net.process(oc)
-            ec.backup(p.contiguous(), v.contiguous())
-        assert torch.equal(ea.root_counts(), ec.root_counts()), mv
-        assert torch.equal(ea.root_probs(1.0), ec.root_probs(1.0)) and torch.equal(ea.root_value(True), ec.root_value(True)), mv
-        ea.advance(True); ec.advance(True)
-        assert torch.equal(ea.last_actions(), ec.last_actions()), mv
-    assert (ea.tape_counters() == ec.tape_counters()).all()
-    assert ea.counters() == ec.counters()
-    for t, u in zip(ea.examples(), ec.examples()):
-        assert torch.equal(t, u)
-    assert all((a == b).all() for a, b in zip(ea.results(), ec.results()))
-    ea.close(); ec.close()
+    FC.twin_moves(GB, B, lambda ea: net._hip.search(ea, sims, exact=True), lambda ec, oc: net.process(oc), sims, moves,
+                  cpuct=4.0, fpu_reduction=0.4, add_root_noise=True, add_root_temp=True, seed=41)
 
 
-def test_gb_wide_search_deep_path():
-    """positions about 200 plies in: the walks of the persistent launch reach terminal leaves and full boards (wins, draws at turn 225)
-    through the game-sized walk mailbox, still equal to the per-phase loop"""
-    from alphazero_general_amd.engine import DeviceEngine
-    net = _net('gobang_64x4')
+def _deep_path(net):
+    """64 positions 180 or more plies in, 120 simulations: the persistent launch's root counts and deepest path equal the per-phase loop's"""
     Game = _game()
     rng = np.random.RandomState(11)
     states = []
@@ -345,20 +239,23 @@ def test_gb_wide_search_deep_path():
             g = g2
         if g.turns >= 180:
             states.append(g.to_azg_state())
+    from alphazero_general_amd.engine import DeviceEngine
     sims = 120
     kw = dict(cpuct=4.0, fpu_reduction=0.4, seed=17, games_per_iteration=1 << 30, example_capacity=1 << 14, sims_hint=sims)
     ea, ec = DeviceEngine(GB, 64, **kw), DeviceEngine(GB, 64, **kw)
     ea.set_states(states); ec.set_states(states)
-    oc = ec.new_obs(torch.float32)
     net._hip.search(ea, sims, exact=True)
-    for _ in range(sims):
-        ec.select(oc)
-        p, v = net.process(oc)
-        ec.backup(p.contiguous(), v.contiguous())
-    assert torch.equal(ea.root_counts(), ec.root_counts())
+    FC.phase_loop(ec, lambda ec, oc: net.process(oc), sims, ec.new_obs(torch.float32))
+    FC.assert_engines_equal(ea, ec, ('counts',))             # (one search, no move: this test is about the walk)
     depth = max(ea.tree_info(i)['max_depth'] for i in range(64))
     assert depth >= 3 and depth == max(ec.tree_info(i)['max_depth'] for i in range(64))
     ea.close(); ec.close()
+
+
+def test_gb_wide_search_deep_path():
+    """positions about 200 plies in: the walks of the persistent launch reach terminal leaves and full boards (wins, draws at turn 225)
+    through the game-sized walk mailbox, still equal to the per-phase loop"""
+    _deep_path(_net('gobang_64x4'))
 
 
 def _flat_net(key, salt=7):
@@ -399,39 +296,22 @@ def test_gb_wide_exact_search_at_exact_ties():
     B = len(ks) * per_k
     assert B == 48
     states = _sparse_draw_states(ks, per_k, 23)
-    kw = dict(cpuct=1.25, fpu_reduction=-1.0, seed=43, games_per_iteration=1 << 30, example_capacity=B * (moves + 1) * 8, sims_hint=sims)
-    ea, ec, ep = DeviceEngine(GB, B, **kw), DeviceEngine(GB, B, **kw), DeviceEngine(GB, B, **kw)
-    ea.set_states(states); ec.set_states(states); ep.set_states(states)
-    oc = ec.new_obs(torch.float32)
-    ep.select(oc)                                           # (a third engine: the twins' tapes stay in step)
+    ep = DeviceEngine(GB, B, seed=43)                       # (an engine of its own: the twins' tapes stay in step)
+    ep.set_states(states)
+    oc = ep.new_obs(torch.float32)
+    ep.select(oc)
     p, v = net.process(oc)                                  # the network really ties: every row's entries are equal bit for bit
     ep.close()
     assert p.shape == (B, A) and v.shape == (B, NV)
     assert bool((p == p[:, :1]).all()) and bool((v == v[:, :1]).all()) and bool((p > 0).all())
-    wide = 0
-    for mv in range(moves):
-        net._hip.search(ea, sims, exact=True)
-        for _ in range(sims):
-            ec.select(oc)
-            p, v = net.process(oc)
-            ec.backup(p.contiguous(), v.contiguous())
-        ca = ea.root_counts()
-        assert torch.equal(ca, ec.root_counts()), mv
-        assert torch.equal(ea.root_probs(1.0), ec.root_probs(1.0)) and torch.equal(ea.root_value(True), ec.root_value(True)), mv
-        assert torch.equal(ea.root_value(False), ec.root_value(False)), mv
-        assert mv > 0 or int(ca.sum()) == B * (sims - 1)         # (later moves search on in the kept subtree)
-        for i in range(B):                                  # visits landed on list indices past the first chunk
-            ch = ea.root_children(i)
-            wide += int((ch['n'][64:] > 0).sum())
-        ea.advance(True); ec.advance(True)
-        assert torch.equal(ea.last_actions(), ec.last_actions()), mv
-    assert wide > 0
-    assert (ea.tape_counters() == ec.tape_counters()).all()
-    assert ea.counters() == ec.counters()
-    for t, u in zip(ea.examples(), ec.examples()):
-        assert torch.equal(t, u)
-    assert all((a == b).all() for a, b in zip(ea.results(), ec.results()))
-    ea.close(); ec.close()
+    wide = []
+
+    def spread(ea, ec, mv):
+        assert mv > 0 or int(ea.root_counts().sum()) == B * (sims - 1)         # (later moves search on in the kept subtree)
+        wide.extend(int((ea.root_children(i)['n'][64:] > 0).sum()) for i in range(B))    # visits landed on list indices past the first chunk
+    FC.twin_moves(GB, B, lambda ea: net._hip.search(ea, sims, exact=True), lambda ec, oc: net.process(oc), sims, moves, states,
+                  each_move=spread, cpuct=1.25, fpu_reduction=-1.0, seed=43)
+    assert sum(wide) > 0
 
 
 # ------------------------------------------------------------------------------------------------------------------------- arena

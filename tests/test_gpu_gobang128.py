@@ -9,10 +9,10 @@ streamed through a short register ring, csrc/azg_conv.h heads_full_stream).  Bit
     the games replayed on envs.gobang;
   * routing: fused_search=True takes the persistent form, fused_search=None follows HipResNet.search_preferred, and the sparse
     persistent launch still refuses gobang."""
-import numpy as np
 import pytest
 import torch
 
+import fixture_checks as FC
 import test_gpu_arena_wide as W
 import test_gpu_gobang as TG
 
@@ -31,64 +31,18 @@ def _net(depth, salt=7):
 @pytest.mark.parametrize('B,sims,moves', [(320, 40, 3), (24, 30, 4)])
 @pytest.mark.parametrize('depth', [8, 1])
 def test_gb128_wide_exact_search_vs_phase_loop(depth, B, sims, moves):
-    """one persistent launch per move against the per-phase loop on a twin engine: root counts, root_probs(1.0), root_value(True) and
+    """one persistent launch per move against the per-phase loop on a twin engine: root counts, root_probs(1.0), both root values and
     the moves after every move; tape counters, counters, examples and results at the end"""
-    from alphazero_general_amd.engine import DeviceEngine
     net = _net(depth)
     assert net._hip.can_search
-    kw = dict(cpuct=4.0, fpu_reduction=0.4, add_root_noise=True, add_root_temp=True, seed=41, games_per_iteration=1 << 30,
-              example_capacity=B * (moves + 1) * 8, sims_hint=sims)
-    ea, ec = DeviceEngine(GB, B, **kw), DeviceEngine(GB, B, **kw)
-    oc = ec.new_obs(torch.float32)
-    for mv in range(moves):
-        net._hip.search(ea, sims, exact=True)
-        for _ in range(sims):
-            ec.select(oc)
-            p, v = net.process(oc)
-            ec.backup(p.contiguous(), v.contiguous())
-        assert torch.equal(ea.root_counts(), ec.root_counts()), mv
-        assert torch.equal(ea.root_probs(1.0), ec.root_probs(1.0)) and torch.equal(ea.root_value(True), ec.root_value(True)), mv
-        ea.advance(True); ec.advance(True)
-        assert torch.equal(ea.last_actions(), ec.last_actions()), mv
-    assert (ea.tape_counters() == ec.tape_counters()).all()
-    assert ea.counters() == ec.counters()
-    for t, u in zip(ea.examples(), ec.examples()):
-        assert torch.equal(t, u)
-    assert all((a == b).all() for a, b in zip(ea.results(), ec.results()))
-    ea.close(); ec.close()
+    FC.twin_moves(GB, B, lambda ea: net._hip.search(ea, sims, exact=True), lambda ec, oc: net.process(oc), sims, moves,
+                  cpuct=4.0, fpu_reduction=0.4, add_root_noise=True, add_root_temp=True, seed=41)
 
 
 def test_gb128_wide_search_deep_path():
-    """64 positions 180 or more plies in (built as test_gpu_gobang.test_gb_wide_search_deep_path builds them), 120 simulations: the
+    """64 positions 180 or more plies in (test_gpu_gobang._deep_path, on this net), 120 simulations: the
     persistent launch's walks reach terminal leaves and full boards, root counts and the deepest path equal the per-phase loop's"""
-    from alphazero_general_amd.engine import DeviceEngine
-    net = _net(8)
-    Game = TG._game()
-    rng = np.random.RandomState(11)
-    states = []
-    while len(states) < 64:
-        g = Game()
-        for a in rng.permutation(A)[:200]:
-            g2 = g.clone(); g2.play_action(int(a))
-            if g2.win_state().any():
-                continue
-            g = g2
-        if g.turns >= 180:
-            states.append(g.to_azg_state())
-    sims = 120
-    kw = dict(cpuct=4.0, fpu_reduction=0.4, seed=17, games_per_iteration=1 << 30, example_capacity=1 << 14, sims_hint=sims)
-    ea, ec = DeviceEngine(GB, 64, **kw), DeviceEngine(GB, 64, **kw)
-    ea.set_states(states); ec.set_states(states)
-    oc = ec.new_obs(torch.float32)
-    net._hip.search(ea, sims, exact=True)
-    for _ in range(sims):
-        ec.select(oc)
-        p, v = net.process(oc)
-        ec.backup(p.contiguous(), v.contiguous())
-    assert torch.equal(ea.root_counts(), ec.root_counts())
-    depth = max(ea.tree_info(i)['max_depth'] for i in range(64))
-    assert depth >= 3 and depth == max(ec.tree_info(i)['max_depth'] for i in range(64))
-    ea.close(); ec.close()
+    TG._deep_path(_net(8))
 
 
 @pytest.mark.parametrize('raw', [False, True])

@@ -9,55 +9,32 @@ the checkers, and every comparison is equality.
     has no network (warm-up), through azg_search_raw;
   * azg_search_raw against sims x [azg_select(NULL), azg_backup] at 1, 3 and 64 slots; forced compaction; slot export / import;
   * the MCTS class on the host env; a SelfPlayRunner round with a PyTorch network (no tower is built for this game)."""
-import os
-import zlib
-
 import numpy as np
 import pytest
 import torch
 
-import oracle_lib as ol
+import fixture_checks as FC
 import test_gpu_parity as P
 import test_gpu_raw_search as RS
+from fixture_checks import crc, crc_rows, load as _load
 
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 HN, DEV, A, NV, CELLS = 6, 'cuda:0', 2420, 3, 121
-PROB_TEMPS = [1.0, 0.5, 0.25, 0.2, 0.0]
-# MCTS.probs is compared where its power is exact on both sides: temperature 1 (x), 0.5 (x * x) and 0 (one-hot).  At 0.25 and 0.2 numpy calls
-# the C library's float32 powf, which is within an ulp but not correctly rounded, and np_pow_f32 (csrc/azg_device.h, shared by every game)
-# rounds a double pow: on hn_tree's `cpuct4` trace ONE of 14 520 entries differs by an ulp at 0.25 -- the tier that file documents
-EXACT_TEMPS = (0, 1, 4)
-
-
-def crc(a):
-    return zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
-
-
-def crc_rows(a):
-    a = np.ascontiguousarray(a)
-    return np.array([crc(r) for r in a.reshape(-1, a.shape[-1])], np.uint32).reshape(a.shape[:-1])
+PROB_TEMPS = [1.0, 0.5, 0.25, 0.2, 0.0]                       # (hn_edge.npz does not hold its probs columns' temperatures: make_goldens.PROB_TEMPS)
+# This game's tier of fixture_checks.TREE.  The fixtures hold the 2420-wide rows as crcs, so MCTS.probs is compared where its power is exact
+# on both sides: temperature 1 (x), 0.5 (x * x) and 0 (one-hot).  At 0.25 and 0.2 numpy calls the C library's float32 powf, which is within
+# an ulp but not correctly rounded, and np_pow_f32 (csrc/azg_device.h, shared by every game) rounds a double pow: on hn_tree's `cpuct4` trace
+# ONE of 14 520 entries differs by an ulp at 0.25 -- the tier a crc cannot carry.
+# p_ulps: priors under ROOT TEMPERATURE are p ** (1 / 1.1) renormalised (MCTS.pyx:249-252): numpy's float32 powf again.  Both powers are
+# within one ulp of the true value, so is their float32 sum (every term is), and the quotient rounds once more: the two priors are at most
+# 4 ulps apart -- and must be, everything downstream of them (PUCT choices, counts, q, v) is compared exactly
+HN_TREE = dict(FC.TREE, p_ulps=4)                             # (rootn crcs: of the fixture's int16 rows)
+HN_EDGE = dict(HN_TREE, rootn_crc_dtype=np.int32, has_k=True)  # crcs of int32 rows; up to 448 children kept, and the root's child count
 
 
 def _game():
     from alphazero_general_amd.envs.hnefatafl import Game
     return Game
-
-
-def _load(name):
-    return dict(np.load(os.path.join(G, name + '.npz')))
-
-
-def _states(prefix):
-    Game = _game()
-    out = []
-    for row in prefix:
-        g = Game()
-        for a in row:
-            if a >= 0:
-                g.play_action(int(a))
-        out.append(g.to_azg_state())
-    return out
 
 
 def _edge_states(d, rows=None):
@@ -118,68 +95,13 @@ def test_hn_rules_vs_reference_tables():
 
 
 # ------------------------------------------------------------------------------------------------------------------------- tree / edge
-def _sim(eng, launch, s, sims, pol, val, obs):
-    """simulation s's backup (and, fused, simulation s + 1's select)"""
-    if launch == 'fused' and s + 1 < sims:
-        eng.backup_select(pol, val, obs)
-    else:
-        eng.backup(pol, val)
-        if launch == 'phase' and s + 1 < sims:
-            eng.select(obs)
-
-
-def _final_checks(eng, d, cname, R_, kmax):
-    # priors under ROOT TEMPERATURE are p ** (1 / 1.1) renormalised (MCTS.pyx:249-252): numpy's float32 powf again (see EXACT_TEMPS).  Both
-    # powers are within one ulp of the true value, so is their float32 sum (every term is), and the quotient rounds once more: the two
-    # priors are at most 4 ulps apart -- and must be, everything downstream of them (PUCT choices, counts, q, v) is compared exactly
-    root_temp = bool(d[cname + '_cfg'][3])
-    for r in range(R_):
-        ch = eng.root_children(r)
-        k = len(ch['a'])
-        kk = min(k, kmax)
-        if cname + '_k' in d:
-            assert k == d[cname + '_k'][r]
-        assert (ch['a'][:kk] == d[cname + '_a'][r][:kk]).all() and (d[cname + '_a'][r][kk:] == -1).all()
-        assert (ch['n'][:kk] == d[cname + '_n'][r][:kk]).all()
-        for f in ('q', 'v') if root_temp else ('q', 'p', 'v'):
-            assert (ch[f][:kk] == d[cname + '_' + f][r][:kk]).all(), (f, r)
-        if root_temp:
-            got, want = ch['p'][:kk], d[cname + '_p'][r][:kk]
-            assert (np.abs(got.astype(np.float64) - want) <= 4 * np.spacing(np.maximum(got, want))).all(), ('p', r)
-        info = eng.tree_info(r)
-        assert info['n'] == d[cname + '_root_n'][r] and info['max_depth'] == d[cname + '_maxdepth'][r]
-    assert (crc_rows(eng.root_counts().cpu().numpy()) == d[cname + '_counts_crc']).all()
-    for ti in EXACT_TEMPS:
-        assert (crc_rows(eng.root_probs(PROB_TEMPS[ti]).cpu().numpy()) == d[cname + '_probs_crc'][:, ti]).all(), PROB_TEMPS[ti]
-    assert (eng.root_value(False).cpu().numpy() == d[cname + '_vmax']).all()
-    assert (eng.root_value(True).cpu().numpy() == d[cname + '_vavg']).all()
-    assert (eng.tape_counters() == d[cname + '_ctr']).all()
-    eng.counters()
-
-
 @pytest.mark.parametrize('launch', P.LAUNCHES)
 @pytest.mark.parametrize('cname', ['default', 'cpuct4', 'temp'])
 def test_hn_tree_vs_reference_goldens(cname, launch):
     d = _load('hn_tree')
-    cpuct, fpu, noise, temp, sims = d[cname + '_cfg']
-    sims, seed, R_ = int(sims), int(d[cname + '_seed']), d['prefix'].shape[0]
-    eng = P.engine(game=HN, B=R_, cpuct=cpuct, fpu_reduction=fpu, add_root_noise=bool(noise), add_root_temp=bool(temp), seed=seed,
-                   sims_hint=sims, nodes_per_tree=sims * 448 + 64)
-    eng.set_states(_states(d['prefix']))
-    obs = eng.new_obs()
-    eng.select(obs)
-    for s in range(sims):
-        for r in range(R_):
-            path = eng.last_path(r)
-            assert len(path) == d[cname + '_depth'][r, s]
-            assert (path[:24] == d[cname + '_paths'][r, s][:len(path)]).all(), (r, s)
-        pol, val = P.fake_batch(torch, seed, range(R_), s, A, NV, eng.device)
-        _sim(eng, launch, s, sims, pol, val, obs)
-        if launch == 'phase':                                 # (fused: the next find_leaf has run; the counts are the same)
-            assert (crc_rows(eng.root_counts().cpu().numpy().astype(np.int16)) == d[cname + '_rootn_crc'][:, s]).all(), s
-    assert all(len(eng.root_children(r)['a']) > 64 for r in range(R_))
-    _final_checks(eng, d, cname, R_, d[cname + '_a'].shape[1])
-    eng.close()
+    sims = int(d[cname + '_cfg'][4])
+    tr, = FC.check_tree(HN, d, cname, FC.states_from_prefix(_game(), d['prefix']), HN_TREE, 'hn', None, [launch], nodes_per_tree=sims * 448 + 64)
+    assert all(len(a) > 64 for a in tr['a'])
 
 
 @pytest.mark.parametrize('launch', P.LAUNCHES)
@@ -189,26 +111,10 @@ def test_hn_edge_vs_reference_goldens(cname, launch):
     and roots at turns 508..511, where leaves meet the turn-512 draw inside the tree; noise_temp: Dirichlet noise over up to 257 children
     (alpha = 10.83 / k: some draws are float32 denormals) and root temperature"""
     d = _load('hn_edge')
-    cpuct, fpu, noise, temp, sims = d[cname + '_cfg']
-    sims, seed, R_ = int(sims), int(d[cname + '_seed']), len(d['player'])
+    sims = int(d[cname + '_cfg'][4])
     assert {64, 65, 128, 129, 192, 193, 256, 257, -508, -509, -510, -511} <= set(d['kind'].tolist())
     assert (d[cname + '_k'][:8] == d['kind'][:8]).all() and (d[cname + '_leaf_e'][d['kind'] < 0] == 4).any()
-    eng = P.engine(game=HN, B=R_, cpuct=cpuct, fpu_reduction=fpu, add_root_noise=bool(noise), add_root_temp=bool(temp), seed=seed,
-                   sims_hint=sims, nodes_per_tree=sims * 448 + 64)
-    eng.set_states(_edge_states(d))
-    obs = eng.new_obs()
-    eng.select(obs)
-    for s in range(sims):
-        for r in range(R_):
-            path = eng.last_path(r)
-            assert len(path) == d[cname + '_depth'][r, s]
-            assert (path[:8] == d[cname + '_paths'][r, s][:len(path)]).all(), (r, s)
-        pol, val = P.fake_batch(torch, seed, range(R_), s, A, NV, eng.device)
-        _sim(eng, launch, s, sims, pol, val, obs)
-        if launch == 'phase':
-            assert (crc_rows(eng.root_counts().cpu().numpy()) == d[cname + '_rootn_crc'][:, s]).all(), s
-    _final_checks(eng, d, cname, R_, 448)
-    eng.close()
+    FC.check_tree(HN, d, cname, _edge_states(d), HN_EDGE, 'hn_edge', None, [launch], prob_temps=PROB_TEMPS, nodes_per_tree=sims * 448 + 64)
 
 
 # ------------------------------------------------------------------------------------------------------------------------- agent
@@ -219,71 +125,17 @@ AGENT = {'plain': (dict(symmetric_samples=False), dict()),
          'long': (dict(symmetric_samples=False), dict())}
 
 
-def _run_agent(eng, seed, slot_base, sims, games, launch, prob_fast=0.0, fast_sims=20, warmup=False, warmup_sims=5, max_rounds=2200):
-    """SelfPlayAgent.run on the engine (as test_gpu_parity.run_engine_agent), with the rows kept as CRCs; launch 'raw': a warm-up round as
-    ONE azg_search_raw launch"""
-    from alphazero_general_amd import _abi
-    from alphazero_general_amd.utils import AGENT_STREAM
-    L = _abi.lib()
-    B = eng.B
-    rec = dict(actions=[], counts_crc=[], obs_crc=[], games_played=[], sims=[])
-    obs = eng.new_obs()
-    step, actr, gp = 0, 0, 0
-    wp = torch.full((B, A), 1 / A, dtype=torch.float32, device=eng.device)
-    wv = torch.full((B, NV), 1 / NV, dtype=torch.float32, device=eng.device)
-    for _ in range(max_rounds):
-        if gp >= games:
-            break
-        fast = L.azg_tape_uniform(seed, AGENT_STREAM + slot_base, actr) < prob_fast
-        actr += 1
-        ns = fast_sims if fast else (warmup_sims if warmup else sims)
-        rec['sims'].append(ns)
-        if launch == 'raw':
-            eng.search_raw(ns, float(np.float32(1 / A)), np.full(NV, 1 / NV, np.float32))
-        else:
-            eng.select(None if warmup else obs)
-            for s in range(ns):
-                if warmup:
-                    pol, val = wp, wv
-                else:
-                    rec['obs_crc'].append(crc_rows(obs.cpu().numpy().reshape(B, -1)))
-                    pol, val = P.fake_batch(torch, seed, [slot_base + i for i in range(B)], step, A, NV, eng.device)
-                _sim(eng, launch, s, ns, pol, val, None if warmup else obs)
-                step += 1
-        rec['counts_crc'].append(crc_rows(eng.root_counts().cpu().numpy()))
-        eng.advance(record_history=not fast)
-        rec['actions'].append(eng.last_actions().cpu().numpy())
-        gp = eng.counters()['games_played']
-        rec['games_played'].append(gp)
-    return rec
-
-
 @pytest.mark.parametrize('cname,launch', [(c, l) for c in AGENT for l in P.LAUNCHES] + [('warmup', 'raw')])
 def test_hn_agent_vs_reference_goldens(cname, launch):
     """whole reference SelfPlayAgent runs, move for move and sample for sample; `long` plays until a game ends in the turn-512 draw: a
-    513-entry history and paths through turn 512"""
+    513-entry history and paths through turn 512; launch 'raw': a warm-up round as ONE azg_search_raw launch"""
     d = _load('hn_agent')
-    B, sims, games = int(d[cname + '_B']), int(d[cname + '_sims']), int(d[cname + '_games'])
-    seed, slot_base = int(d[cname + '_seed']), int(d[cname + '_slot_base'])
     kw, rnd = AGENT[cname]
-    eng = P.engine(game=HN, B=B, seed=seed, slot_base=slot_base, games_per_iteration=games, example_capacity=8192, sims_hint=max(sims, 5),
-                   nodes_per_tree=16 * 5 * 448 + 64, **kw)
-    rec = _run_agent(eng, seed, slot_base, sims, games, launch, **rnd)
-    assert (np.array(rec['sims']) == d[cname + '_round_sims']).all()
-    assert (np.array(rec['counts_crc']) == d[cname + '_counts_crc']).all()
-    assert (np.array(rec['actions']) == d[cname + '_actions']).all()
-    assert (np.array(rec['games_played']) == d[cname + '_games_played']).all()
-    if cname != 'warmup':
-        assert (np.array(rec['obs_crc'], np.uint32).reshape(-1, B) == d[cname + '_obs_crc']).all()
-    obs, pi, z = [t.cpu().numpy() for t in eng.examples()]
-    n = len(d[cname + '_s_z'])
-    assert len(z) == n and (z == d[cname + '_s_z']).all()
-    assert (crc_rows(obs.reshape(n, -1)) == d[cname + '_s_obs_crc']).all() and (crc_rows(pi) == d[cname + '_s_pi_crc']).all()
-    ws, turns, _ = eng.results()
-    assert (ws == d[cname + '_r_ws']).all() and (turns == d[cname + '_r_turns']).all()
+    rec = FC.check_agent(HN, d, cname + '_', launch, 'hn', max_rounds=2200, **rnd,
+                         engine_kw=dict(kw, example_capacity=8192, sims_hint=max(int(d[cname + '_sims']), 5), nodes_per_tree=16 * 5 * 448 + 64))
     if cname == 'long':
+        ws, turns = rec['r_ws'], rec['r_turns']
         assert 512 in turns.tolist() and ws[turns.tolist().index(512)].tolist() == [0, 0, 1]
-    eng.close()
 
 
 # ------------------------------------------------------------------------------------------------------------------------- raw search
@@ -401,24 +253,11 @@ def test_hn_mcts_class_api_vs_reference_goldens():
     from alphazero_general_amd.utils import dotdict
     d = _load('hn_tree')
     cpuct, fpu, _, _, sims = d['default_cfg']
-    seed, sims = int(d['default_seed']), int(sims)
-    Game = _game()
-    g = Game.from_azg_state(*_states(d['prefix'][:1])[0])
+    seed, Game = int(d['default_seed']), _game()
+    m, g = FC.check_mcts_class(Game, d, A, NV, search=True, tier=HN_TREE, game='hn')
+    assert m._engine.nodes_per_tree * 64 <= NODE_STORE_BUDGET                               # (a default object: 256 MB, not max_turns moves' worth)
     args = dotdict(cpuct=float(cpuct), fpu_reduction=float(fpu), root_noise_frac=0.1, root_policy_temp=1.1, min_discount=1, _num_players=3,
-                   numMCTSSims=sims, _azg_seed=seed)
-    m = MCTS(args)
-    calls = []
-
-    def nn(o):
-        assert o.shape == (5, 11, 11)
-        calls.append(1)
-        return ol.fake_eval(seed, 0, len(calls) - 1, A, NV)
-    m.search(g, nn, sims, False, False)
-    assert len(calls) == sims and m._engine.nodes_per_tree * 64 <= NODE_STORE_BUDGET        # (a default object: 256 MB, not max_turns moves' worth)
-    assert crc(np.asarray(m.counts(g)).astype(np.int32)) == d['default_counts_crc'][0]
-    assert m.value(False) == d['default_vmax'][0] and m.value(True) == d['default_vavg'][0] and m.max_depth == d['default_maxdepth'][0]
-    for ti in EXACT_TEMPS:
-        assert crc(np.asarray(m.probs(g, PROB_TEMPS[ti]), np.float32)) == d['default_probs_crc'][0, ti]
+                   numMCTSSims=int(sims), _azg_seed=seed)
     c0 = np.asarray(m.counts(g))
     a = m.best_action(g)
     m.update_root(g, a)

@@ -16,8 +16,8 @@ import numpy as np
 import pytest
 import torch
 
+import fixture_checks as FC
 import net_reference as R
-import oracle_lib as ol
 import test_gpu_net_fp64 as F
 import test_gpu_parity as P
 import test_gpu_rules as GR
@@ -33,18 +33,6 @@ def _game():
     return Game
 
 
-def _states(prefix):
-    Game = _game()
-    out = []
-    for row in prefix:
-        g = Game()
-        for a in row:
-            if a >= 0:
-                g.play_action(int(a))
-        out.append(g.to_azg_state())
-    return out
-
-
 # ------------------------------------------------------------------------------------------------------------------------- rules
 def test_ot_rules_vs_reference_tables():
     d = dict(np.load(os.path.join(G, 'ot_rules.npz')))
@@ -55,43 +43,8 @@ def test_ot_rules_vs_reference_tables():
 # ------------------------------------------------------------------------------------------------------------------------- tree / agent
 @pytest.mark.parametrize('cname', ['default', 'cpuct4', 'noise_temp'])
 def test_ot_tree_vs_reference_goldens(cname):
-    d = dict(np.load(os.path.join(G, 'ot_tree.npz')))
-    cpuct, fpu, noise, temp, sims = d[cname + '_cfg']
-    noise, temp, sims = bool(noise), bool(temp), int(sims)
-    seed = int(d[cname + '_seed'])
-    R_, A, NV = d['prefix'].shape[0], 64, 3
-    exact = not temp
-    eng = P.engine(game=OT, B=R_, cpuct=cpuct, fpu_reduction=fpu, add_root_noise=noise, add_root_temp=temp, seed=seed, sims_hint=sims)
-    eng.set_states(_states(d['prefix']))
-    obs = eng.new_obs()
-    for s in range(sims):
-        eng.select(obs)
-        for r in range(R_):
-            path = eng.last_path(r)
-            assert len(path) == d[cname + '_depth'][r, s]
-            assert (path[:24] == d[cname + '_paths'][r, s][:len(path)]).all(), (r, s)
-        pol, val = P.fake_batch(torch, seed, range(R_), s, A, NV, eng.device)
-        eng.backup(pol, val)
-        assert (eng.root_counts().cpu().numpy() == d[cname + '_rootn'][:, s]).all(), s
-    for r in range(R_):
-        ch = eng.root_children(r)
-        k = len(ch['a'])
-        assert (ch['a'] == d[cname + '_a'][r][:k]).all() and (d[cname + '_a'][r][k:] == -1).all() and (ch['n'] == d[cname + '_n'][r][:k]).all()
-        for f in ('q', 'p', 'v'):
-            if exact:
-                assert (ch[f] == d[cname + '_' + f][r][:k]).all(), (f, r)
-            else:
-                assert np.allclose(ch[f], d[cname + '_' + f][r][:k], atol=1e-5), (f, r)
-        info = eng.tree_info(r)
-        assert info['n'] == d[cname + '_root_n'][r] and info['max_depth'] == d[cname + '_maxdepth'][r]
-    assert (eng.root_counts().cpu().numpy() == d[cname + '_counts']).all()
-    assert (eng.root_probs(1.0).cpu().numpy() == d[cname + '_probs'][:, 0]).all()
-    assert (eng.root_probs(0.0).cpu().numpy() == d[cname + '_probs'][:, 4]).all()
-    assert (eng.root_value(False).cpu().numpy() == d[cname + '_vmax']).all()
-    assert (eng.root_value(True).cpu().numpy() == d[cname + '_vavg']).all()
-    assert (eng.tape_counters() == d[cname + '_ctr']).all()
-    eng.counters()
-    eng.close()
+    d = FC.load('ot_tree')
+    FC.check_tree(OT, d, cname, FC.states_from_prefix(_game(), d['prefix']), FC.TREE, 'ot')
 
 
 AGENT = {'plain': (dict(), dict()),
@@ -102,67 +55,19 @@ AGENT = {'plain': (dict(), dict()),
 @pytest.mark.parametrize('launch', P.LAUNCHES)
 @pytest.mark.parametrize('cname', list(AGENT))
 def test_ot_agent_vs_reference_goldens(cname, launch):
-    d = dict(np.load(os.path.join(G, 'ot_agent.npz')))
-    B, sims, games = int(d[cname + '_B']), int(d[cname + '_sims']), int(d[cname + '_games'])
-    seed, slot_base = int(d[cname + '_seed']), int(d[cname + '_slot_base'])
     kw, rnd = AGENT[cname]
-    eng = P.engine(game=OT, B=B, seed=seed, slot_base=slot_base, games_per_iteration=games, example_capacity=8192, sims_hint=sims, **kw)
-    rec = P.run_engine_agent(torch, eng, seed, slot_base, sims, games, launch=launch, **rnd)
-    assert (np.array(rec['sims']) == d[cname + '_round_sims']).all()
-    assert (np.array(rec['counts']) == d[cname + '_counts']).all()
-    assert (np.array(rec['actions']) == d[cname + '_actions']).all()
-    assert (np.array(rec['games_played']) == d[cname + '_games_played']).all()
-    assert (np.array(rec['obs_crc'], np.uint32) == d[cname + '_obs_crc']).all()
-    obs, pi, z = [t.cpu().numpy() for t in eng.examples()]
-    assert obs.shape == d[cname + '_s_obs'].shape
-    assert (obs == d[cname + '_s_obs']).all() and (pi == d[cname + '_s_pi']).all() and (z == d[cname + '_s_z']).all()
-    ws, turns, _ = eng.results()
-    assert (ws == d[cname + '_r_ws']).all() and (turns == d[cname + '_r_turns']).all()
-    eng.close()
+    FC.check_agent(OT, FC.load('ot_agent'), cname + '_', launch, 'ot', engine_kw=dict(kw, example_capacity=8192), **rnd)
 
 
 @pytest.mark.parametrize('launch', P.LAUNCHES)
 def test_ot_selfplay_agent_under_numpys_mt19937_seed(launch):
-    d = dict(np.load(os.path.join(G, 'ot_mt19937_agent.npz')))
-    B, sims, games, eseed = int(d['B']), int(d['sims']), int(d['games']), int(d['eval_seed'])
-    cpuct, fpu, nfrac, rtemp = [float(x) for x in d['cfg']]
-    eng = P.engine(game=OT, B=B, cpuct=cpuct, fpu_reduction=fpu, root_noise_frac=nfrac, root_policy_temp=rtemp, add_root_noise=True,
-                   add_root_temp=True, seed=987654321, games_per_iteration=games, example_capacity=4096, sims_hint=sims)
-    eng.set_random_tape(d['tape_ranks'], d['tape_u'], d['tape_noise_off'], d['tape_noise_pool'])
-    rec = P.run_engine_agent(torch, eng, eseed, 0, sims, games, launch=launch)
-    n = len(d['actions'])
-    assert len(rec['actions']) == n and (np.array(rec['games_played']) == d['games_played']).all()
-    for r in range(n):
-        assert (np.asarray(rec['counts'][r]) == d['counts'][r]).all(), (launch, r)
-        assert (np.asarray(rec['actions'][r]) == d['actions'][r]).all(), (launch, r)
-    eo, ep, ez = [t.cpu().numpy() for t in eng.examples()]
-    assert eo.shape == d['s_obs'].shape and (eo == d['s_obs']).all() and (ez == d['s_z']).all() and (ep == d['s_pi']).all()
-    ws, turns, _ = eng.results()
-    assert (ws == d['r_ws']).all() and (turns == d['r_turns']).all()
-    eng.set_shuffle_tape(None)
-    eng.close()
+    FC.check_mt19937_agent(OT, FC.load('ot_mt19937_agent'), launch, 'ot')
 
 
 def test_ot_mcts_class_api_vs_reference_goldens():
     """alphazero_general_amd.MCTS on an envs.othello.Game object (one slot: the tape stream of ot_tree's root 0), find_leaf /
     process_results fed the fixture's evaluations, must build the reference's tree: paths, root children, counts, values"""
-    from alphazero_general_amd.MCTS import MCTS
-    from alphazero_general_amd.utils import dotdict
-    d = dict(np.load(os.path.join(G, 'ot_tree.npz')))
-    cpuct, fpu, _, _, sims = d['default_cfg']
-    seed, sims = int(d['default_seed']), int(sims)
-    g = _states(d['prefix'][:1])[0]
-    g = _game().from_azg_state(*g)
-    m = MCTS(dotdict(cpuct=float(cpuct), fpu_reduction=float(fpu), root_noise_frac=0.1, root_policy_temp=1.1, min_discount=1,
-                     _num_players=3, numMCTSSims=sims, _azg_seed=seed))
-    for s in range(sims):
-        leaf = m.find_leaf(g)
-        assert m.depth == d['default_depth'][0, s]
-        p, v = ol.fake_eval(seed, 0, s, 64, 3)
-        m.process_results(leaf, v, p, False, False)
-    assert (np.asarray(m.counts(g)) == d['default_counts'][0]).all()
-    assert m.value(False) == d['default_vmax'][0] and m.value(True) == d['default_vavg'][0]
-    assert (np.asarray(m.probs(g, 1.0), np.float32) == d['default_probs'][0, 0]).all()
+    FC.check_mcts_class(_game(), FC.load('ot_tree'), 64, 3, game='ot')
 
 
 # ------------------------------------------------------------------------------------------------------------------------- network
@@ -245,28 +150,9 @@ def _net(key, salt=7):
 def test_ot_wide_exact_search_vs_phase_loop(key, B, sims, moves):
     """azg_search_wide_exact_f16 against select -> NNetWrapper.process -> backup on a twin engine with the same seeds: every slot's
     counts, moves, samples and results identical"""
-    from alphazero_general_amd.engine import DeviceEngine
     net = _net(key)
-    kw = dict(cpuct=4.0, fpu_reduction=0.4, add_root_noise=True, add_root_temp=True, seed=41, games_per_iteration=1 << 30,
-              example_capacity=B * (moves + 1) * 8, sims_hint=sims)
-    ea, ec = DeviceEngine(OT, B, **kw), DeviceEngine(OT, B, **kw)
-    oc = ec.new_obs(torch.float32)
-    for mv in range(moves):
-        net._hip.search(ea, sims, exact=True)
-        for _ in range(sims):
-            ec.select(oc)
-            p, v = net.process(oc)
-            ec.backup(p.contiguous(), v.contiguous())
-        assert torch.equal(ea.root_counts(), ec.root_counts()), mv
-        assert torch.equal(ea.root_probs(1.0), ec.root_probs(1.0)) and torch.equal(ea.root_value(True), ec.root_value(True)), mv
-        ea.advance(True); ec.advance(True)
-        assert torch.equal(ea.last_actions(), ec.last_actions()), mv
-    assert (ea.tape_counters() == ec.tape_counters()).all()
-    assert ea.counters() == ec.counters()
-    for t, u in zip(ea.examples(), ec.examples()):
-        assert torch.equal(t, u)
-    assert all((a == b).all() for a, b in zip(ea.results(), ec.results()))
-    ea.close(); ec.close()
+    FC.twin_moves(OT, B, lambda ea: net._hip.search(ea, sims, exact=True), lambda ec, oc: net.process(oc), sims, moves,
+                  cpuct=4.0, fpu_reduction=0.4, add_root_noise=True, add_root_temp=True, seed=41)
 
 
 def test_ot_wide_exact_search_at_exact_ties():
@@ -281,36 +167,20 @@ def test_ot_wide_exact_search_at_exact_ties():
     sd = {k: (torch.zeros_like(v) if k.rsplit('.', 1)[0] in last else v) for k, v in sd.items()}
     assert sum(1 for k in sd if k.rsplit('.', 1)[0] in last) == 4 and sd[last[0] + '.weight'].shape[0] == 64
     net = _wrapper(args, sd)
-    roots = ee.roots(dict(np.load(os.path.join(G, 'ot_edge.npz'))), OT)
+    roots = ee.roots(FC.load('ot_edge'), OT)
     ks = [int(g.valid_moves().sum()) for g in roots]
     assert {1, 2} <= set(ks) and max(ks) >= 8
     states = [g.to_azg_state() for g in roots] * 4
     B, sims, moves = len(states), 60, 2
-    kw = dict(cpuct=1.25, fpu_reduction=-1.0, seed=47, games_per_iteration=1 << 30, example_capacity=B * (moves + 1) * 8, sims_hint=sims)
-    ea, ec, ep = DeviceEngine(OT, B, **kw), DeviceEngine(OT, B, **kw), DeviceEngine(OT, B, **kw)
-    ea.set_states(states); ec.set_states(states); ep.set_states(states)
-    oc = ec.new_obs(torch.float32)
-    ep.select(oc)                                           # (a third engine: the twins' tapes stay in step)
+    ep = DeviceEngine(OT, B, seed=47)                       # (an engine of its own: the twins' tapes stay in step)
+    ep.set_states(states)
+    oc = ep.new_obs(torch.float32)
+    ep.select(oc)
     p, v = net.process(oc)                                  # the network really ties: every row's entries are equal bit for bit
     ep.close()
     assert p.shape == (B, 64) and bool((p == p[:, :1]).all()) and bool((v == v[:, :1]).all()) and bool((p > 0).all())
-    for mv in range(moves):
-        net._hip.search(ea, sims, exact=True)
-        for _ in range(sims):
-            ec.select(oc)
-            p, v = net.process(oc)
-            ec.backup(p.contiguous(), v.contiguous())
-        assert torch.equal(ea.root_counts(), ec.root_counts()), mv
-        assert torch.equal(ea.root_probs(1.0), ec.root_probs(1.0)) and torch.equal(ea.root_value(True), ec.root_value(True)), mv
-        assert torch.equal(ea.root_value(False), ec.root_value(False)), mv
-        ea.advance(True); ec.advance(True)
-        assert torch.equal(ea.last_actions(), ec.last_actions()), mv
-    assert (ea.tape_counters() == ec.tape_counters()).all()
-    assert ea.counters() == ec.counters()
-    for t, u in zip(ea.examples(), ec.examples()):
-        assert torch.equal(t, u)
-    assert all((a == b).all() for a, b in zip(ea.results(), ec.results()))
-    ea.close(); ec.close()
+    FC.twin_moves(OT, B, lambda ea: net._hip.search(ea, sims, exact=True), lambda ec, oc: net.process(oc), sims, moves, states,
+                  cpuct=1.25, fpu_reduction=-1.0, seed=47)
 
 
 @pytest.mark.parametrize('key', list(NETS))
@@ -319,23 +189,11 @@ def test_ot_wide_sparse_search_vs_phase_loop(key):
     from alphazero_general_amd.engine import DeviceEngine
     net = _net(key)
     hip = net._hip
-    B, sims, moves = 512, 50, 3
-    kw = dict(cpuct=1.25, fpu_reduction=0.2, add_root_noise=True, add_root_temp=True, seed=29, games_per_iteration=1 << 30,
-              example_capacity=B * (moves + 1) * 8, sims_hint=sims)
-    ea, ec = DeviceEngine(OT, B, **kw), DeviceEngine(OT, B, **kw)
-    oc = ec.new_obs(torch.float32)
-    for mv in range(moves):
-        hip.search(ea, sims)
-        for _ in range(sims):
-            ec.select(oc)
-            lg = ec.leaf_heads_sparse(hip.forward_features_nhwc8(hip.to_nhwc8(oc), key=2), hip.head_rows, hip.head2_b)
-            p, v = ec.heads_softmax(lg)
-            ec.backup(p, v)
-        assert torch.equal(ea.root_counts(), ec.root_counts()), mv
-        ea.advance(True); ec.advance(True)
-        assert torch.equal(ea.last_actions(), ec.last_actions()), mv
-    assert ea.counters() == ec.counters()
-    ea.close(); ec.close()
+    # counts, moves and counters: the comparisons this test has always made of the sparse-heads launch, passed by name -- widening it to
+    # probabilities, values, samples and results is left to a change of its own
+    FC.twin_moves(OT, 512, lambda ea: hip.search(ea, 50), lambda ec, oc: ec.heads_softmax(ec.leaf_heads_sparse(
+        hip.forward_features_nhwc8(hip.to_nhwc8(oc), key=2), hip.head_rows, hip.head2_b)), 50, 3, searched=('counts',), finished=('counters',),
+        cpuct=1.25, fpu_reduction=0.2, add_root_noise=True, add_root_temp=True, seed=29)
 
 
 def test_ot_sparse_heads_vs_fp64():

@@ -5,20 +5,17 @@ plus size-independent properties at BASELINE.json's full size (2048 games x 100 
 Bars: visit counts, actions, paths, pi(T=1), samples bit-exact; q/v bit-exact in the exact tier (no root
 temperature), atol 1e-5 otherwise; pi(T not in {1, .5, 0}) within rtol 3e-7 (powf tier)."""
 import os
-import zlib
 
 import numpy as np
 import pytest
 
+import fixture_checks as FC
 import oracle_lib as ol
+from fixture_checks import LAUNCHES, crc                     # (other test modules take them from here)
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 C4 = 0
-
-
-def crc(a):
-    return zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
 
 
 @pytest.fixture(scope='module')
@@ -40,68 +37,17 @@ def ostate(g):
 
 
 def fake_batch(torch, seed, slots, step, A, NV, dev):
-    pol = np.zeros((len(slots), A), np.float32); val = np.zeros((len(slots), NV), np.float32)
-    for r, s in enumerate(slots):
-        pol[r], val[r] = ol.fake_eval(seed, int(s), step, A, NV)
+    pol, val = FC.fake_rows(seed, slots, step, A, NV)
     return torch.from_numpy(pol).to(dev), torch.from_numpy(val).to(dev)
 
 
 # ------------------------------------------------------------------------------------------------- tree goldens
 @pytest.mark.parametrize('cname', ['default', 'c4train', 'noise', 'noise_temp'])
 def test_c4_tree_vs_reference_goldens(torch_mod, cname):
-    torch = torch_mod
-    d = dict(np.load(os.path.join(G, 'c4_tree.npz')))              # (NpzFile decompresses an array on EVERY d[key])
-    cpuct, fpu, noise, temp, sims = d[cname + '_cfg']
-    noise, temp, sims = bool(noise), bool(temp), int(sims)
-    seed = int(d[cname + '_seed'])
-    R = d['prefix'].shape[0]
-    A, NV = 7, 3
-    exact = not temp
-    eng = engine(B=R, cpuct=cpuct, fpu_reduction=fpu, add_root_noise=noise, add_root_temp=temp, seed=seed, sims_hint=sims)
-    states = []
-    for r in range(R):
-        g = ol.OGame(C4)
-        for a in d['prefix'][r]:
-            if a >= 0:
-                g.play(a)
-        states.append(ostate(g))
-    eng.set_states(states)
-    obs = eng.new_obs()
-    for s in range(sims):
-        eng.select(obs)
-        for r in range(0, R, 7):                      # spot-check leaf paths every sim on a subset of roots (every root: tests/test_gpu_tree_edges.py)
-            path = eng.last_path(r)
-            assert len(path) == d[cname + '_depth'][r, s]
-            assert (path[:24] == d[cname + '_paths'][r, s][:len(path)]).all(), (r, s)
-        pol, val = fake_batch(torch, seed, range(R), s, A, NV, eng.device)
-        eng.backup(pol, val)
-        cnt = eng.root_counts().cpu().numpy()
-        assert (cnt == d[cname + '_rootn'][:, s]).all(), s
-    for r in range(R):
-        ch = eng.root_children(r)
-        k = len(ch['a'])
-        assert (ch['a'] == d[cname + '_a'][r][:k]).all() and (d[cname + '_a'][r][k:] == -1).all()
-        assert (ch['n'] == d[cname + '_n'][r][:k]).all()
-        for f in ('q', 'p', 'v'):
-            if exact:
-                assert (ch[f] == d[cname + '_' + f][r][:k]).all(), (f, r)
-            else:
-                assert np.allclose(ch[f], d[cname + '_' + f][r][:k], atol=1e-5), (f, r)
-        info = eng.tree_info(r)
-        assert info['n'] == d[cname + '_root_n'][r] and info['max_depth'] == d[cname + '_maxdepth'][r]
-    assert (eng.root_counts().cpu().numpy() == d[cname + '_counts']).all()
-    for ti, t in enumerate(d['prob_temps']):
-        pr = eng.root_probs(float(t)).cpu().numpy()
-        ref = d[cname + '_probs'][:, ti]
-        if t in (1.0, 0.5, 0.0):
-            assert (pr == ref).all(), t
-        else:
-            assert np.allclose(pr, ref, rtol=3e-7, atol=1e-12), t
-    assert (eng.root_value(False).cpu().numpy() == d[cname + '_vmax']).all()
-    assert (eng.root_value(True).cpu().numpy() == d[cname + '_vavg']).all()
-    assert (eng.tape_counters() == d[cname + '_ctr']).all()
-    eng.counters()
-    eng.close()
+    # path_stride: leaf paths on every seventh root -- 64 roots x 100 simulations x 4 configs x 2 launch forms of one-path reads that find
+    # nothing the smaller games' every-root reads do not (every root: tests/test_gpu_tree_edges.py)
+    d = FC.load('c4_tree')
+    FC.check_tree(C4, d, cname, FC.oracle_states_from_prefix(C4, d['prefix']), FC.TREE, 'c4', path_stride=7)
 
 
 def test_c4_search_under_numpys_mt19937_seed(torch_mod):
@@ -114,32 +60,17 @@ def test_c4_search_under_numpys_mt19937_seed(torch_mod):
     R, sims, eseed = d['prefix'].shape[0], int(d['sims']), int(d['eval_seed'])
     A, NV = 7, 3
     eng = engine(B=R, cpuct=float(d['cfg'][0]), fpu_reduction=float(d['cfg'][1]), add_root_noise=False, add_root_temp=False, seed=12345, sims_hint=sims)
-    states = []
-    for r in range(R):
-        g = ol.OGame(C4)
-        for a in d['prefix'][r]:
-            if a >= 0:
-                g.play(a)
-        states.append(ostate(g))
+    states = FC.oracle_states_from_prefix(C4, d['prefix'])
     eng.set_states(states)
     eng.set_shuffle_tape(d['ranks'])
     obs = eng.new_obs()
-    for launch in ('phase', 'fused'):
+    for launch in LAUNCHES:
         if launch == 'fused':                              # the two-wavefront launch (backup k + select k + 1) replays the same tape
             eng.set_states(states); eng.set_tape_counters([0] * R)
-        if launch == 'phase':
-            for s in range(sims):
-                eng.select(obs)
-                pol, val = fake_batch(torch, eseed, range(R), s, A, NV, eng.device)
-                eng.backup(pol, val)
-        else:
-            eng.select(obs)
-            for s in range(sims):
-                pol, val = fake_batch(torch, eseed, range(R), s, A, NV, eng.device)
-                if s + 1 < sims:
-                    eng.backup_select(pol, val, obs)
-                else:
-                    eng.backup(pol, val)
+        eng.select(obs)
+        for s in range(sims):
+            pol, val = fake_batch(torch, eseed, range(R), s, A, NV, eng.device)
+            FC.sim_step(eng, launch, s, sims, pol, val, obs)
         for r in range(R):
             ch = eng.root_children(r)
             k = len(ch['a'])
@@ -164,37 +95,11 @@ def test_c4_search_under_numpys_mt19937_seed(torch_mod):
 @pytest.mark.parametrize('name', ['c4', 'br'])
 @pytest.mark.parametrize('launch', ['phase', 'fused'])
 def test_c4_selfplay_agent_under_numpys_mt19937_seed(torch_mod, launch, name):
-    """A whole SelfPlayAgent under np.random.seed(s), move for move: tests/golden/c4_mt19937_agent.npz is the REFERENCE's
-    agent -- 4 concurrent connect4 games, root noise and root temperature on, 6 games -- on numpy's own MT19937 stream with shuffle /
-    dirichlet / choice observed per game slot (tests/test_oracle_golden.py re-derives every draw from the seed alone).  The engine replays
-    all three (azg_set_random_tape) and must reproduce: visit counts and the sampled action of every slot in every round, the games_played
-    trajectory, the (state, pi, z) samples incl. symmetries and the results in queue order, and end with its tape counters at the end of
-    each slot's recorded draws.  (Temperatures other than 1 go through powf: counts and actions are compared exactly, as in the agent
+    """fixture_checks.check_mt19937_agent on c4_mt19937_agent.npz -- 4 concurrent connect4 games, root noise and root
+    temperature on, 6 games.  (Temperatures other than 1 go through powf: counts and actions are compared exactly, as in the agent
     goldens.)  name = 'br': the same for the reference's second game -- br_mt19937_agent.npz, 4 brandubh games over 53 rounds, 3 329 recorded
     shuffles of 40-100 children (lists longer than a wavefront), 8-fold symmetries in the samples."""
-    torch = torch_mod
-    d = dict(np.load(os.path.join(G, name + '_mt19937_agent.npz')))
-    B, sims, games, eseed = int(d['B']), int(d['sims']), int(d['games']), int(d['eval_seed'])
-    cpuct, fpu, nfrac, rtemp = [float(x) for x in d['cfg']]
-    eng = engine(game={'c4': C4, 'br': ol.GAME_BRANDUBH}[name], B=B, cpuct=cpuct, fpu_reduction=fpu, root_noise_frac=nfrac, root_policy_temp=rtemp,
-                 add_root_noise=True, add_root_temp=True, seed=987654321, games_per_iteration=games, example_capacity=4096, sims_hint=sims)
-    eng.set_random_tape(d['tape_ranks'], d['tape_u'], d['tape_noise_off'], d['tape_noise_pool'])
-    rec = run_engine_agent(torch, eng, eseed, 0, sims, games, launch=launch)
-    n = len(d['actions'])
-    assert len(rec['actions']) == n and (np.array(rec['games_played']) == d['games_played']).all()
-    for r in range(n):
-        assert (np.asarray(rec['counts'][r]) == d['counts'][r]).all(), (launch, r)
-        assert (np.asarray(rec['actions'][r]) == d['actions'][r]).all(), (launch, r)
-    eo, ep, ez = [t.cpu().numpy() for t in eng.examples()]
-    assert eo.shape == d['s_obs'].shape and (eo == d['s_obs']).all() and (ez == d['s_z']).all()
-    assert np.allclose(ep, d['s_pi'], rtol=0, atol=0) and (ep == d['s_pi']).all()         # pi at T = 1 is counts / sum: exact
-    ws, turns, _ = eng.results()
-    assert (ws == d['r_ws']).all() and (turns == d['r_turns']).all()
-    used = [int((d['call_order'][(d['call_order'][:, 1] == sl) & (d['call_order'][:, 0] == 0), 2]).sum()
-                + ((d['call_order'][:, 1] == sl) & (d['call_order'][:, 0] > 0)).sum()) for sl in range(B)]
-    assert (eng.tape_counters() == np.array(used, np.uint64)).all()
-    eng.set_shuffle_tape(None)
-    eng.close()
+    FC.check_mt19937_agent({'c4': C4, 'br': ol.GAME_BRANDUBH}[name], FC.load(name + '_mt19937_agent'), launch, name)
 
 
 # ------------------------------------------------------------------------------------------------ agent goldens
@@ -209,79 +114,11 @@ AGENT_CFGS = {
 AGENT_ROUND = {'fastmix': dict(prob_fast=0.5, fast_sims=6), 'warmup': dict(warmup=True, warmup_sims=5)}
 
 
-def run_engine_agent(torch, eng, seed, slot_base, sims, games, prob_fast=0.0, fast_sims=20, warmup=False, warmup_sims=5,
-                     max_rounds=500, launch='phase'):
-    """SelfPlayAgent.run (SelfPlayAgent.pyx:79-101) on the engine.  launch = 'phase': generateBatch / processBatch as azg_select /
-    azg_backup; 'fused': backup k and select k + 1 share a launch (azg_backup_select: k_backup_select2, two wavefronts per tree) --
-    the form every runner and bench line uses."""
-    from alphazero_general_amd.utils import AGENT_STREAM
-    from alphazero_general_amd import _abi
-    L = _abi.lib()
-    B, A, NV = eng.B, eng.A, eng.NV
-    rec = dict(actions=[], counts=[], obs_crc=[], games_played=[], sims=[])
-    obs = eng.new_obs()
-    step, actr = 0, 0
-    wp = torch.full((B, A), 1 / A, dtype=torch.float32, device=eng.device)
-    wv = torch.full((B, NV), 1 / NV, dtype=torch.float32, device=eng.device)
-    gp = 0
-    for _ in range(max_rounds):
-        if gp >= games:
-            break
-        fast = L.azg_tape_uniform(seed, AGENT_STREAM + slot_base, actr) < prob_fast
-        actr += 1
-        ns = fast_sims if fast else (warmup_sims if warmup else sims)
-        rec['sims'].append(ns)
-        if launch == 'fused':
-            eng.select(None if warmup else obs)
-        for s in range(ns):
-            if launch == 'phase':
-                eng.select(None if warmup else obs)
-            if warmup:
-                pol, val = wp, wv
-            else:
-                o = obs.cpu().numpy()
-                rec['obs_crc'].append([crc(o[i]) for i in range(B)])
-                pol, val = fake_batch(torch, seed, [slot_base + i for i in range(B)], step, A, NV, eng.device)
-            if launch == 'fused' and s + 1 < ns:
-                eng.backup_select(pol, val, None if warmup else obs)
-            else:
-                eng.backup(pol, val)
-            step += 1
-        rec['counts'].append(eng.root_counts().cpu().numpy())
-        eng.advance(record_history=not fast)
-        rec['actions'].append(eng.last_actions().cpu().numpy())
-        gp = eng.counters()['games_played']
-        rec['games_played'].append(gp)
-    return rec
-
-
-LAUNCHES = ['phase', 'fused']
-
-
 @pytest.mark.parametrize('launch', LAUNCHES)
 @pytest.mark.parametrize('cname', list(AGENT_CFGS))
 def test_c4_agent_vs_reference_goldens(torch_mod, cname, launch):
-    torch = torch_mod
-    d = dict(np.load(os.path.join(G, 'c4_agent.npz')))              # (NpzFile decompresses an array on EVERY d[key])
-    B, sims, games = int(d[cname + '_B']), int(d[cname + '_sims']), int(d[cname + '_games'])
-    seed, slot_base = int(d[cname + '_seed']), int(d[cname + '_slot_base'])
-    eng = engine(B=B, seed=seed, slot_base=slot_base, games_per_iteration=games, example_capacity=16384, sims_hint=sims,
-                 **AGENT_CFGS[cname])
-    rec = run_engine_agent(torch, eng, seed, slot_base, sims, games, launch=launch, **AGENT_ROUND.get(cname, {}))
-    assert (np.array(rec['sims']) == d[cname + '_round_sims']).all()
-    assert (np.array(rec['counts']) == d[cname + '_counts']).all()
-    assert (np.array(rec['actions']) == d[cname + '_actions']).all()
-    assert (np.array(rec['games_played']) == d[cname + '_games_played']).all()
-    if cname != 'warmup':
-        assert (np.array(rec['obs_crc'], np.uint32) == d[cname + '_obs_crc']).all()
-    obs, pi, z = [t.cpu().numpy() for t in eng.examples()]
-    assert obs.shape == d[cname + '_s_obs'].shape
-    assert (obs == d[cname + '_s_obs']).all()
-    assert (pi == d[cname + '_s_pi']).all()
-    assert (z == d[cname + '_s_z']).all()
-    ws, turns, slot = eng.results()
-    assert (ws == d[cname + '_r_ws']).all() and (turns == d[cname + '_r_turns']).all()
-    eng.close()
+    FC.check_agent(C4, FC.load('c4_agent'), cname + '_', launch, 'c4', engine_kw=dict(AGENT_CFGS[cname], example_capacity=16384),
+                   **AGENT_ROUND.get(cname, {}))
 
 
 # ----------------------------------------------------------------------------------- live oracle, larger sizes
@@ -565,53 +402,10 @@ def test_br_rules_fuzz(torch_mod):
 
 @pytest.mark.parametrize('cname', ['default', 'noise_temp'])
 def test_br_tree_vs_reference_goldens(torch_mod, cname):
-    torch = torch_mod
-    d = dict(np.load(os.path.join(G, 'br_tree.npz')))              # (NpzFile decompresses an array on EVERY d[key])
-    cpuct, fpu, noise, temp, sims = d[cname + '_cfg']
-    noise, temp, sims = bool(noise), bool(temp), int(sims)
-    seed = int(d[cname + '_seed'])
-    R, A, NV = d['prefix'].shape[0], 588, 3
-    exact = not temp
-    eng = engine(game=BR, B=R, cpuct=cpuct, fpu_reduction=fpu, add_root_noise=noise, add_root_temp=temp, seed=seed, sims_hint=sims)
-    states = []
-    for r in range(R):
-        g = ol.OGame(BR)
-        for a in d['prefix'][r]:
-            if a >= 0:
-                g.play(a)
-        states.append((g.cells(), g.player, g.turns, g.s.aux[0]))
-    eng.set_states(states)
-    obs = eng.new_obs()
-    for s in range(sims):
-        eng.select(obs)
-        for r in range(0, R, 5):
-            path = eng.last_path(r)
-            assert len(path) == d[cname + '_depth'][r, s]
-            assert (path[:24] == d[cname + '_paths'][r, s][:len(path)]).all(), (r, s)
-        pol, val = fake_batch(torch, seed, range(R), s, A, NV, eng.device)
-        eng.backup(pol, val)
-        cnt = eng.root_counts().cpu().numpy()
-        assert (cnt == d[cname + '_rootn'][:, s]).all(), s
-    for r in range(R):
-        ch = eng.root_children(r)
-        k = len(ch['a'])
-        assert (ch['a'] == d[cname + '_a'][r][:k]).all() and (ch['n'] == d[cname + '_n'][r][:k]).all()
-        for f in ('q', 'p', 'v'):
-            if exact:
-                assert (ch[f] == d[cname + '_' + f][r][:k]).all(), (f, r)
-            else:
-                assert np.allclose(ch[f], d[cname + '_' + f][r][:k], atol=1e-5), (f, r)
-    for ti, t in enumerate(d['prob_temps']):
-        pr = eng.root_probs(float(t)).cpu().numpy()
-        ref = d[cname + '_probs'][:, ti]
-        if t in (1.0, 0.5, 0.0):
-            assert (pr == ref).all(), t                 # exercises the numpy pairwise-sum plan for A = 588
-        else:
-            assert np.allclose(pr, ref, rtol=3e-7, atol=1e-12), t
-    assert (eng.root_value(False).cpu().numpy() == d[cname + '_vmax']).all()
-    assert (eng.root_value(True).cpu().numpy() == d[cname + '_vavg']).all()
-    assert (eng.tape_counters() == d[cname + '_ctr']).all()
-    eng.close()
+    # path_stride: leaf paths on every fifth root, as this test always read them -- every root of 32, on both launch forms, took the
+    # test from 0.2 s to 1.2 s on the device for paths the edge fixtures' br roots are held to at every simulation
+    d = FC.load('br_tree')                                   # (its probs columns exercise the numpy pairwise-sum plan for A = 588)
+    FC.check_tree(BR, d, cname, FC.oracle_states_from_prefix(BR, d['prefix']), FC.TREE, 'br', path_stride=5)
 
 
 @pytest.mark.parametrize('noise', [False, True])
@@ -712,24 +506,8 @@ def test_prior_spreads_from_denormal_to_one_vs_oracle(torch_mod, game, spread):
 @pytest.mark.parametrize('cname,kw', [('plain', dict()), ('noisy', dict(add_root_noise=True, add_root_temp=True)), ('wide', dict()),
                                       ('raw', dict(symmetric_samples=False))])           # raw: symmetries()[6] is the identity
 def test_br_agent_vs_reference_goldens(torch_mod, cname, kw, launch):
-    torch = torch_mod
-    d = dict(np.load(os.path.join(G, 'br_agent.npz')))              # (NpzFile decompresses an array on EVERY d[key])
-    B, sims, games = int(d[cname + '_B']), int(d[cname + '_sims']), int(d[cname + '_games'])
-    seed, slot_base = int(d[cname + '_seed']), int(d[cname + '_slot_base'])
-    eng = engine(game=BR, B=B, seed=seed, slot_base=slot_base, games_per_iteration=games, example_capacity=20000, sims_hint=sims, **kw)
     rnd = dict(prob_fast=0.5, fast_sims=6) if cname == 'raw' else {}
-    rec = run_engine_agent(torch, eng, seed, slot_base, sims, games, launch=launch, **rnd)
-    assert (np.array(rec['sims']) == d[cname + '_round_sims']).all()
-    assert (np.array(rec['counts']) == d[cname + '_counts']).all()
-    assert (np.array(rec['actions']) == d[cname + '_actions']).all()
-    assert (np.array(rec['games_played']) == d[cname + '_games_played']).all()
-    assert (np.array(rec['obs_crc'], np.uint32) == d[cname + '_obs_crc']).all()
-    obs, pi, z = [t.cpu().numpy() for t in eng.examples()]
-    assert obs.shape == d[cname + '_s_obs'].shape
-    assert (obs == d[cname + '_s_obs']).all() and (pi == d[cname + '_s_pi']).all() and (z == d[cname + '_s_z']).all()
-    ws, turns, slot = eng.results()
-    assert (ws == d[cname + '_r_ws']).all() and (turns == d[cname + '_r_turns']).all()
-    eng.close()
+    FC.check_agent(BR, FC.load('br_agent'), cname + '_', launch, 'br', engine_kw=dict(kw, example_capacity=20000), **rnd)
 
 
 # ------------------------------------------------------------------------------------------------ trimok, 3 players (config 5)
@@ -738,61 +516,14 @@ TM = 2
 
 @pytest.mark.parametrize('cname', ['default', 'noise_temp'])
 def test_tm_tree_vs_reference_goldens(torch_mod, cname):
-    torch = torch_mod
-    d = dict(np.load(os.path.join(G, 'tm_tree.npz')))              # (NpzFile decompresses an array on EVERY d[key])
-    cpuct, fpu, noise, temp, sims = d[cname + '_cfg']
-    noise, temp, sims = bool(noise), bool(temp), int(sims)
-    seed = int(d[cname + '_seed'])
-    R, A, NV = d['prefix'].shape[0], 25, 4
-    exact = not temp
-    eng = engine(game=TM, B=R, cpuct=cpuct, fpu_reduction=fpu, add_root_noise=noise, add_root_temp=temp, seed=seed, sims_hint=sims)
-    states = []
-    for r in range(R):
-        g = ol.OGame(TM)
-        for a in d['prefix'][r]:
-            if a >= 0:
-                g.play(a)
-        states.append(ostate(g))
-    eng.set_states(states)
-    obs = eng.new_obs()
-    for s in range(sims):
-        eng.select(obs)
-        pol, val = fake_batch(torch, seed, range(R), s, A, NV, eng.device)
-        eng.backup(pol, val)
-        assert (eng.root_counts().cpu().numpy() == d[cname + '_rootn'][:, s]).all(), s
-    for r in range(R):
-        ch = eng.root_children(r)
-        k = len(ch['a'])
-        assert (ch['a'] == d[cname + '_a'][r][:k]).all() and (ch['n'] == d[cname + '_n'][r][:k]).all()
-        for f in ('q', 'p', 'v'):
-            if exact:
-                assert (ch[f] == d[cname + '_' + f][r][:k]).all(), (f, r)
-            else:
-                assert np.allclose(ch[f], d[cname + '_' + f][r][:k], atol=1e-5), (f, r)
-    assert (eng.root_probs(1.0).cpu().numpy() == d[cname + '_probs'][:, 0]).all()
-    assert (eng.root_value(False).cpu().numpy() == d[cname + '_vmax']).all()
-    assert (eng.tape_counters() == d[cname + '_ctr']).all()
-    eng.close()
+    d = FC.load('tm_tree')
+    FC.check_tree(TM, d, cname, FC.oracle_states_from_prefix(TM, d['prefix']), FC.TREE, 'tm')
 
 
 @pytest.mark.parametrize('launch', LAUNCHES)
 @pytest.mark.parametrize('cname,kw', [('plain', dict()), ('noisy', dict(add_root_noise=True, add_root_temp=True)), ('wide', dict())])
 def test_tm_agent_vs_reference_goldens(torch_mod, cname, kw, launch):
-    torch = torch_mod
-    d = dict(np.load(os.path.join(G, 'tm_agent.npz')))              # (NpzFile decompresses an array on EVERY d[key])
-    B, sims, games = int(d[cname + '_B']), int(d[cname + '_sims']), int(d[cname + '_games'])
-    seed, slot_base = int(d[cname + '_seed']), int(d[cname + '_slot_base'])
-    eng = engine(game=TM, B=B, seed=seed, slot_base=slot_base, games_per_iteration=games, example_capacity=8000, sims_hint=sims, **kw)
-    rec = run_engine_agent(torch, eng, seed, slot_base, sims, games, launch=launch)
-    assert (np.array(rec['counts']) == d[cname + '_counts']).all()
-    assert (np.array(rec['actions']) == d[cname + '_actions']).all()
-    assert (np.array(rec['games_played']) == d[cname + '_games_played']).all()
-    assert (np.array(rec['obs_crc'], np.uint32) == d[cname + '_obs_crc']).all()
-    obs, pi, z = [t.cpu().numpy() for t in eng.examples()]
-    assert (obs == d[cname + '_s_obs']).all() and (pi == d[cname + '_s_pi']).all() and (z == d[cname + '_s_z']).all()
-    ws, turns, slot = eng.results()
-    assert (ws == d[cname + '_r_ws']).all() and (turns == d[cname + '_r_turns']).all()
-    eng.close()
+    FC.check_agent(TM, FC.load('tm_agent'), cname + '_', launch, 'tm', engine_kw=dict(kw, example_capacity=8000))
 
 
 # --------------------------------------------------- full-size properties of the other BASELINE configs (3 and 5)

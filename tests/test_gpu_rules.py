@@ -9,18 +9,15 @@ through envs/brandubh/fastafl.pyx) -- every position, on the GPU, through the C 
 
 Connect4Logic.pyx:40-110, connect4.pyx:54-91; fastafl/cengine.pyx:109-272, envs/brandubh/fastafl.pyx:48-121,196-211."""
 import os
-import zlib
 
 import numpy as np
 import pytest
 
+from fixture_checks import crc
+
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 C4, BR = 0, 1
-
-
-def crc(a):
-    return zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
 
 
 def _engine(game, B):

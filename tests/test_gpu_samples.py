@@ -51,7 +51,7 @@ class Evaluator:
 
 
 def play(eng, ev, fast, cap=None, target=None):
-    """SelfPlayAgent rounds (SelfPlayAgent.pyx:79-101) on the engine, in the phase form of test_gpu_parity.run_engine_agent.
+    """SelfPlayAgent rounds (SelfPlayAgent.pyx:79-101) on the engine, in the phase form of fixture_checks.run_agent.
     cap: eng.advance until the engine's games_per_iteration cap is met.  target: advance_begin + advance_commit, every finished
     game counted until `target` games have finished; then the first round with two or more finished games skips the ones at
     even positions in slot order, and the run ends there."""

@@ -4,25 +4,24 @@ tests/net_reference.py:
 
   * ALL 39 366 records of tt_rules (every board x both movers, unreachable ones included) through the engine ABI: valid moves, win state,
     observation, and EVERY legal move of every undecided record by a steered second simulation (test_gpu_rules._check_records);
-  * the reference's MCTS (tt_tree: random and uniform priors; tt_edge: exact ties, zero and denormal priors, roots of one and two legal
-    moves), both per-phase launch forms; SelfPlayAgent (tt_agent: raw and symmetric samples, fast rounds, warm-up -- at a temperature
-    that never steps: max_turns() is None) and a whole agent under np.random.seed(s) (tt_mt19937_agent);
+  * the reference's MCTS (tt_tree: random and uniform priors; tt_edge -- exact ties, zero and denormal priors, roots of one and two legal
+    moves -- is the `tt` name of tests/test_gpu_tree_edges.py), both per-phase launch forms; SelfPlayAgent (tt_agent: raw and symmetric
+    samples, fast rounds, warm-up -- at a temperature that never steps: max_turns() is None) and a whole agent under np.random.seed(s)
+    (tt_mt19937_agent) -- all through tests/fixture_checks.py;
   * the tower, head features with their zero padding, logits and probabilities of the default 32 x 4 net (16 + 16 head channels) and of
     TICTACTOE_NET_ARGS (4 + 4, padded) at every tower tile -- one, five and sixteen boards -- and their ragged last tiles;
   * azg_search_wide_exact_f16, azg_search_arena_wide_exact_f16 and azg_search_raw against the launch-per-phase loops, bit for bit;
   * the MCTS class API with pickling, the launch mask against the launches, one self-play iteration and one arena through the runners."""
 import ctypes as C
 import os
-import pickle
-import zlib
 
 import numpy as np
 import pytest
 import torch
 
 import edge_eval as ee
+import fixture_checks as FC
 import net_reference as R
-import oracle_lib as ol
 import test_gpu_arena_wide as AW
 import test_gpu_net_fp64 as F
 import test_gpu_parity as P
@@ -38,18 +37,6 @@ NETS = {'tictactoe_32x4_h4': ('TICTACTOE_NET_ARGS', {}), 'tictactoe_32x4': ('DEF
 def _game():
     from alphazero_general_amd.envs.tictactoe import Game
     return Game
-
-
-def _states(prefix):
-    Game = _game()
-    out = []
-    for row in prefix:
-        g = Game()
-        for a in row:
-            if a >= 0:
-                g.play_action(int(a))
-        out.append(g.to_azg_state())
-    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------------- rules
@@ -86,215 +73,19 @@ def test_tt_rules_every_state_every_move(k, mover):
 TREE_CONFIGS = ['default', 'cpuct2', 'noise', 'noise_temp', 'uniform', 'uniform_noise_temp']
 
 
-def _tree_batch(cname, seed, R_, s, dev):
-    pol, val = P.fake_batch(torch, seed, range(R_), s, A, NV, dev)
-    if cname.startswith('uniform'):                            # (make_tictactoe_goldens.uniform_eval: float32(1) / float32(9), the random value row)
-        pol = torch.full((R_, A), float(np.float32(1.0) / np.float32(A)), dtype=torch.float32, device=dev)
-    return pol, val
-
-
 @pytest.mark.parametrize('cname', TREE_CONFIGS)
 def test_tt_tree_vs_reference_goldens(cname):
-    d = dict(np.load(os.path.join(G, 'tt_tree.npz')))
-    cpuct, fpu, noise, temp, sims = d[cname + '_cfg']
-    noise, temp, sims = bool(noise), bool(temp), int(sims)
-    seed = int(d[cname + '_seed'])
-    R_ = d['prefix'].shape[0]
-    assert 4 <= R_ <= 16 and 8 <= sims <= 30
-    exact = not temp
-    engs = [P.engine(game=TT, B=R_, cpuct=cpuct, fpu_reduction=fpu, add_root_noise=noise, add_root_temp=temp, seed=seed, sims_hint=sims)
-            for _ in range(2)]                                 # [0]: azg_select + azg_backup, [1]: azg_backup_select
-    try:
-        for e in engs:
-            e.set_states(_states(d['prefix']))
-        obs = [e.new_obs() for e in engs]
-        engs[1].select(obs[1])
-        for s in range(sims):
-            engs[0].select(obs[0])
-            assert torch.equal(obs[0], obs[1]), s
-            for r in range(R_):
-                for e in engs:
-                    path = e.last_path(r)
-                    assert len(path) == d[cname + '_depth'][r, s]
-                    assert (path[:24] == d[cname + '_paths'][r, s][:len(path)]).all(), (r, s)
-            pol, val = _tree_batch(cname, seed, R_, s, engs[0].device)
-            engs[0].backup(pol, val)
-            if s + 1 < sims:
-                engs[1].backup_select(pol, val, obs[1])
-            else:
-                engs[1].backup(pol, val)
-            for e in engs:
-                assert (e.root_counts().cpu().numpy() == d[cname + '_rootn'][:, s]).all(), s
-        for e in engs:
-            for r in range(R_):
-                ch = e.root_children(r)
-                k = len(ch['a'])
-                assert (ch['a'] == d[cname + '_a'][r][:k]).all() and (d[cname + '_a'][r][k:] == -1).all() and (ch['n'] == d[cname + '_n'][r][:k]).all()
-                for f in ('q', 'p', 'v'):
-                    if exact:
-                        assert (ch[f] == d[cname + '_' + f][r][:k]).all(), (f, r)
-                    else:
-                        assert np.allclose(ch[f], d[cname + '_' + f][r][:k], atol=1e-5), (f, r)
-                info = e.tree_info(r)
-                assert info['n'] == d[cname + '_root_n'][r] and info['max_depth'] == d[cname + '_maxdepth'][r]
-            assert (e.root_counts().cpu().numpy() == d[cname + '_counts']).all()
-            assert d['prob_temps'].tolist() == [1.0, 0.5, 0.25, float(np.float32(0.2)), 0.0]
-            for ti, t in enumerate(d['prob_temps']):
-                got, want = e.root_probs(float(t)).cpu().numpy(), d[cname + '_probs'][:, ti]
-                if float(t) in (1.0, 0.5, 0.0):                # (as the tree tests of the other games: exact where numpy's power is)
-                    assert (got == want).all(), t
-                else:
-                    assert np.allclose(got, want, rtol=3e-7, atol=1e-12), t
-            assert (e.root_value(False).cpu().numpy() == d[cname + '_vmax']).all()
-            assert (e.root_value(True).cpu().numpy() == d[cname + '_vavg']).all()
-            assert (e.tape_counters() == d[cname + '_ctr']).all()
-            e.counters()
-    finally:
-        for e in engs:
-            e.close()
+    d = FC.load('tt_tree')
+    R_, sims, seed = d['prefix'].shape[0], int(d[cname + '_cfg'][4]), int(d[cname + '_seed'])
+    assert 4 <= R_ <= 16 and 8 <= sims <= 30 and d['prob_temps'].tolist() == [1.0, 0.5, 0.25, float(np.float32(0.2)), 0.0]
+
+    def uniform_rows(s):                                       # (make_tictactoe_goldens.uniform_eval: float32(1) / float32(9), the random value row)
+        return np.full((R_, A), np.float32(1.0) / np.float32(A), np.float32), FC.fake_rows(seed, range(R_), s, A, NV)[1]
+    FC.check_tree(TT, d, cname, FC.states_from_prefix(_game(), d['prefix']), FC.TREE, 'tt', uniform_rows if cname.startswith('uniform') else None)
 
 
-def _edge():
-    return ee.load(G, 'tt')
-
-
-def _edge_roots(d):
-    Game = _game()
-    return [Game.from_azg_state(d['cells'][r], int(d['player'][r]), int(d['turns'][r])) for r in range(len(d['player']))]
-
-
-def _check_probs(pr, d, cname, ti, t):
-    for r in range(len(pr)):
-        ref = d[cname + '_probs'][r][ti]
-        if d[cname + '_probs_raised'][r][ti]:
-            assert np.allclose(pr[r], ee.probs_untrapped(d[cname + '_counts'][r], t), rtol=3e-7, atol=1e-12, equal_nan=True), (r, t)
-        elif t in (1.0, 2.0, 0.5, 0.0):
-            assert (pr[r] == ref).all(), (r, t)
-        else:
-            assert np.allclose(pr[r], ref, rtol=3e-7, atol=1e-12), (r, t)
-
-
-@pytest.mark.parametrize('cname', ee.CONFIGS)
-def test_tt_edge_tree_vs_reference_goldens(cname):
-    """tests/test_gpu_tree_edges.py's check on tt_edge.npz: exact PUCT ties (uniform rows), zero priors (one-hot rows), denormal priors
-    (spread rows), cpuct 0 / 50, fpu_reduction -1 / 0, noise_frac 1, root temperatures 0.5 / 2 / 1.1, on random roots and on roots with
-    one legal move (one move from a full board) and two; both per-phase launch forms"""
-    from alphazero_general_amd.engine import DeviceEngine
-    d = _edge()
-    cpuct, fpu, nfrac, rtemp, sims = d[cname + '_cfg']
-    noise, temp, sims = bool(nfrac > 0), bool(rtemp > 0), int(sims)
-    fam, seed = str(d[cname + '_family']), int(d[cname + '_seed'])
-    exact = not temp or rtemp in (2.0, 0.5)
-    roots = _edge_roots(d)
-    R_ = len(roots)
-    ks = sorted(int(g.valid_moves().sum()) for g in roots)
-    assert 4 <= R_ <= 16 and 8 <= sims <= 30 and ks[:4] == [1, 1, 2, 2] and ks[-1] == 9
-    a_of = d[cname + '_a']
-    engs = [DeviceEngine(TT, R_, cpuct=float(cpuct), fpu_reduction=float(fpu), root_noise_frac=float(nfrac) if noise else 0.1,
-                         root_policy_temp=float(rtemp) if temp else 1.1, add_root_noise=noise, add_root_temp=temp, seed=seed,
-                         sims_hint=sims) for _ in range(2)]
-    try:
-        for e in engs:
-            e.set_states([g.to_azg_state() for g in roots])
-        engs[1].select(None)
-        for s in range(sims):
-            engs[0].select(None)
-            pol = np.zeros((R_, A), np.float32); val = np.zeros((R_, NV), np.float32)
-            for r in range(R_):
-                dep = int(d[cname + '_depth'][r, s])
-                ref = d[cname + '_paths'][r, s][:dep]
-                for e in engs:
-                    path = e.last_path(r)
-                    assert len(path) == dep and (path == ref).all(), (r, s)
-                pol[r], val[r] = ee.leaf_row(fam, seed, roots[r], r, s, ref, A, NV)
-                assert ee.row_crc(pol[r], val[r]) == d[cname + '_row_crc'][r, s], (r, s)
-            tp, tv = torch.from_numpy(pol).to(engs[0].device), torch.from_numpy(val).to(engs[0].device)
-            engs[0].backup(tp, tv)
-            if s + 1 < sims:
-                engs[1].backup_select(tp, tv, None)
-            else:
-                engs[1].backup(tp, tv)
-            want = np.zeros((R_, A), np.int32)
-            for r in range(R_):
-                k = int((a_of[r] >= 0).sum())
-                want[r, a_of[r][:k]] = d[cname + '_rootn'][r, s][:k]
-            for e in engs:
-                assert (e.root_counts().cpu().numpy() == want).all(), s
-        for e in engs:
-            for r in range(R_):
-                ch = e.root_children(r)
-                k = len(ch['a'])
-                assert (ch['a'] == a_of[r][:k]).all() and (a_of[r][k:] == -1).all()
-                assert (ch['n'] == d[cname + '_n'][r][:k]).all()
-                for f in ('q', 'p', 'v'):
-                    if exact:
-                        assert (ch[f] == d[cname + '_' + f][r][:k]).all(), (f, r)
-                    else:
-                        assert np.allclose(ch[f], d[cname + '_' + f][r][:k], atol=1e-5), (f, r)
-                info = e.tree_info(r)
-                assert info['n'] == d[cname + '_root_n'][r] and info['max_depth'] == d[cname + '_maxdepth'][r], r
-            assert (e.root_counts().cpu().numpy() == d[cname + '_counts']).all()
-            for ti, t in enumerate(d['prob_temps']):
-                _check_probs(e.root_probs(float(t)).cpu().numpy(), d, cname, ti, float(t))
-            assert (e.root_value(False).cpu().numpy() == d[cname + '_vmax']).all()
-            assert (e.root_value(True).cpu().numpy() == d[cname + '_vavg']).all()
-            assert (e.tape_counters() == d[cname + '_ctr']).all()
-            e.counters()
-    finally:
-        for e in engs:
-            e.close()
-
-
-def _zero_temp(cur_temp, turns, const_max_turns):
-    return 0
-
-
-@pytest.mark.parametrize('launch', P.LAUNCHES)
-def test_tt_edge_agent_vs_reference_goldens(launch):
-    """the edge agent of tt_edge.npz: uniform priors, draw-heavy values, temperature 0 from the first move (np.argmax ties over the visit
-    counts), symmetric samples on"""
-    from alphazero_general_amd.engine import DeviceEngine
-    d = _edge()
-    B, sims, games, seed = int(d['agent_B']), int(d['agent_sims']), int(d['agent_games']), int(d['agent_seed'])
-    assert 4 <= B <= 8
-    eng = DeviceEngine(TT, B, seed=seed, games_per_iteration=games, example_capacity=4096, sims_hint=sims, start_temp=0.0, temp_fn=_zero_temp)
-    try:
-        rec = dict(actions=[], counts=[], games_played=[], obs_crc=[])
-        step, gp = 0, 0
-        obs = eng.new_obs()
-        for _ in range(len(d['agent_actions'])):
-            assert gp < games
-            if launch == 'fused':
-                eng.select(obs)
-            for s in range(sims):
-                if launch == 'phase':
-                    eng.select(obs)
-                o = obs.cpu().numpy()
-                rec['obs_crc'].append([zlib.crc32(np.ascontiguousarray(o[i]).tobytes()) & 0xFFFFFFFF for i in range(B)])
-                pol = np.zeros((B, A), np.float32); val = np.zeros((B, NV), np.float32)
-                for i in range(B):
-                    pol[i], val[i] = ee.agent_row(seed, i, step, A, NV)
-                tp, tv = torch.from_numpy(pol).to(eng.device), torch.from_numpy(val).to(eng.device)
-                if launch == 'fused' and s + 1 < sims:
-                    eng.backup_select(tp, tv, obs)
-                else:
-                    eng.backup(tp, tv)
-                step += 1
-            rec['counts'].append(eng.root_counts().cpu().numpy())
-            eng.advance(record_history=True)
-            rec['actions'].append(eng.last_actions().cpu().numpy())
-            gp = eng.counters()['games_played']
-            rec['games_played'].append(gp)
-        assert gp == games
-        assert (np.array(rec['counts']) == d['agent_counts']).all() and (np.array(rec['actions']) == d['agent_actions']).all()
-        assert (np.array(rec['games_played']) == d['agent_games_played']).all()
-        assert (np.array(rec['obs_crc'], np.uint32) == d['agent_obs_crc']).all()
-        o, pi, z = [t.cpu().numpy() for t in eng.examples()]
-        assert o.shape == d['agent_s_obs'].shape and (o == d['agent_s_obs']).all() and (pi == d['agent_s_pi']).all() and (z == d['agent_s_z']).all()
-        ws, turns, _ = eng.results()
-        assert (ws == d['agent_r_ws']).all() and (turns == d['agent_r_turns']).all()
-    finally:
-        eng.close()
+def _edge_roots():
+    return ee.roots(FC.load('tt_edge'), TT)
 
 
 # ------------------------------------------------------------------------------------------------------------------------- agent
@@ -310,73 +101,26 @@ def test_tt_agent_vs_reference_goldens(cname, launch):
     """whole reference SelfPlayAgent runs, move for move and sample for sample.  The engine's DEFAULT temperature schedule is used: the
     fixture's moves are those of a temperature that stays at startTemp (the generator asserted that a schedule halving after every move
     -- what azg_game_info.max_turns = 9 would give -- samples other moves from round `<config>_halving_differs_at` on)"""
-    d = dict(np.load(os.path.join(G, 'tt_agent.npz')))
-    B, sims, games = int(d[cname + '_B']), int(d[cname + '_sims']), int(d[cname + '_games'])
-    seed, slot_base = int(d[cname + '_seed']), int(d[cname + '_slot_base'])
-    assert 4 <= B <= 8
+    d = FC.load('tt_agent')
     kw, rnd = AGENT[cname]
-    eng = P.engine(game=TT, B=B, seed=seed, slot_base=slot_base, games_per_iteration=games, example_capacity=4096, sims_hint=sims, **kw)
-    assert (eng._tt == np.float32(1.0)).all() and len(eng._tt) == 11
-    rec = P.run_engine_agent(torch, eng, seed, slot_base, sims, games, launch=launch, **rnd)
-    assert (np.array(rec['sims']) == d[cname + '_round_sims']).all()
-    assert (np.array(rec['counts']) == d[cname + '_counts']).all()
-    assert (np.array(rec['actions']) == d[cname + '_actions']).all()
-    assert (np.array(rec['games_played']) == d[cname + '_games_played']).all()
-    if cname != 'warmup':
-        assert (np.array(rec['obs_crc'], np.uint32) == d[cname + '_obs_crc']).all()
+
+    def default_schedule(eng):
+        assert 4 <= eng.B <= 8 and (eng._tt == np.float32(1.0)).all() and len(eng._tt) == 11
+    rec = FC.check_agent(TT, d, cname + '_', launch, 'tt', engine_kw=dict(kw, example_capacity=4096), before=default_schedule, **rnd)
     if cname in ('plain', 'symmetric'):
         assert int(d[cname + '_halving_differs_at']) < len(rec['actions'])
-    obs, pi, z = [t.cpu().numpy() for t in eng.examples()]
-    assert obs.shape == d[cname + '_s_obs'].shape
-    assert (obs == d[cname + '_s_obs']).all() and (pi == d[cname + '_s_pi']).all() and (z == d[cname + '_s_z']).all()
-    ws, turns, _ = eng.results()
-    assert (ws == d[cname + '_r_ws']).all() and (turns == d[cname + '_r_turns']).all()
-    eng.close()
 
 
 @pytest.mark.parametrize('launch', P.LAUNCHES)
 def test_tt_selfplay_agent_under_numpys_mt19937_seed(launch):
-    d = dict(np.load(os.path.join(G, 'tt_mt19937_agent.npz')))
-    B, sims, games, eseed = int(d['B']), int(d['sims']), int(d['games']), int(d['eval_seed'])
-    cpuct, fpu, nfrac, rtemp = [float(x) for x in d['cfg']]
-    eng = P.engine(game=TT, B=B, cpuct=cpuct, fpu_reduction=fpu, root_noise_frac=nfrac, root_policy_temp=rtemp, add_root_noise=True,
-                   add_root_temp=True, seed=987654321, games_per_iteration=games, example_capacity=4096, sims_hint=sims)
-    eng.set_random_tape(d['tape_ranks'], d['tape_u'], d['tape_noise_off'], d['tape_noise_pool'])
-    rec = P.run_engine_agent(torch, eng, eseed, 0, sims, games, launch=launch)
-    n = len(d['actions'])
-    assert len(rec['actions']) == n and (np.array(rec['games_played']) == d['games_played']).all()
-    for r in range(n):
-        assert (np.asarray(rec['counts'][r]) == d['counts'][r]).all(), (launch, r)
-        assert (np.asarray(rec['actions'][r]) == d['actions'][r]).all(), (launch, r)
-    eo, ep, ez = [t.cpu().numpy() for t in eng.examples()]
-    assert eo.shape == d['s_obs'].shape and (eo == d['s_obs']).all() and (ez == d['s_z']).all() and (ep == d['s_pi']).all()
-    ws, turns, _ = eng.results()
-    assert (ws == d['r_ws']).all() and (turns == d['r_turns']).all()
-    eng.set_shuffle_tape(None)
-    eng.close()
+    FC.check_mt19937_agent(TT, FC.load('tt_mt19937_agent'), launch, 'tt')
 
 
 def test_tt_mcts_class_api_vs_reference_goldens_with_pickling():
     """alphazero_general_amd.MCTS on an envs.tictactoe.Game object (one slot: the tape stream of tt_tree's root 0 -- the empty board),
     find_leaf / process_results fed the fixture's evaluations, pickled and restored half way, must build the reference's tree"""
-    from alphazero_general_amd.MCTS import MCTS
-    from alphazero_general_amd.utils import dotdict
-    d = dict(np.load(os.path.join(G, 'tt_tree.npz')))
-    cpuct, fpu, _, _, sims = d['default_cfg']
-    seed, sims = int(d['default_seed']), int(sims)
-    g = _game().from_azg_state(*_states(d['prefix'][:1])[0])
-    m = MCTS(dotdict(cpuct=float(cpuct), fpu_reduction=float(fpu), root_noise_frac=0.1, root_policy_temp=1.1, min_discount=1,
-                     _num_players=3, numMCTSSims=sims, _azg_seed=seed))
-    for s in range(sims):
-        if s == sims // 2:
-            m = pickle.loads(pickle.dumps(m))
-        leaf = m.find_leaf(g)
-        assert m.depth == d['default_depth'][0, s] and type(leaf) is _game()
-        p, v = ol.fake_eval(seed, 0, s, A, NV)
-        m.process_results(leaf, v, p, False, False)
-    assert (np.asarray(m.counts(g)) == d['default_counts'][0]).all()
-    assert m.value(False) == d['default_vmax'][0] and m.value(True) == d['default_vavg'][0]
-    assert (np.asarray(m.probs(g, 1.0), np.float32) == d['default_probs'][0, 0]).all()
+    d = FC.load('tt_tree')
+    m, g = FC.check_mcts_class(_game(), d, A, NV, pickle_at=int(d['default_cfg'][4]) // 2, game='tt')
     a = m.best_action(g)
     m.update_root(g, a)
     g.play_action(a)
@@ -475,32 +219,11 @@ def _net(key, salt=7):
 def _twin_search(net, B, sims, moves, states=None, **kw):
     """azg_search_wide_exact_f16 against select -> NNetWrapper.process -> backup on a twin engine with the same seeds: every slot's counts,
     probabilities, values, moves, samples and results identical"""
-    from alphazero_general_amd.engine import DeviceEngine
-    kw = dict(dict(seed=41, games_per_iteration=1 << 30, example_capacity=B * (moves + 1) * 8, sims_hint=sims), **kw)
-    ea, ec = DeviceEngine(TT, B, **kw), DeviceEngine(TT, B, **kw)
-    try:
-        if states is not None:
-            ea.set_states(states); ec.set_states(states)
-        oc = ec.new_obs(torch.float32)
-        for mv in range(moves):
-            net._hip.search(ea, sims, exact=True)
-            for _ in range(sims):
-                ec.select(oc)
-                p, v = net.process(oc)
-                ec.backup(p.contiguous(), v.contiguous())
-            assert torch.equal(ea.root_counts(), ec.root_counts()), mv
-            assert torch.equal(ea.root_probs(1.0), ec.root_probs(1.0)) and torch.equal(ea.root_value(True), ec.root_value(True)), mv
-            assert torch.equal(ea.root_value(False), ec.root_value(False)), mv
-            ea.advance(True); ec.advance(True)
-            assert torch.equal(ea.last_actions(), ec.last_actions()), mv
-        assert (ea.tape_counters() == ec.tape_counters()).all()
-        assert ea.counters() == ec.counters() and ea.counters()['sims'] == B * sims * moves
-        for t, u in zip(ea.examples(), ec.examples()):
-            assert torch.equal(t, u)
-        assert all((a == b).all() for a, b in zip(ea.results(), ec.results()))
-        return net._hip.search_tile(ea, exact=True)
-    finally:
-        ea.close(); ec.close()
+    tile = []
+    ca, _ = FC.twin_moves(TT, B, lambda ea: net._hip.search(ea, sims, exact=True), lambda ec, oc: net.process(oc), sims, moves, states,
+                          each_move=lambda ea, ec, mv: tile.append(net._hip.search_tile(ea, exact=True)), **dict(dict(seed=41), **kw))
+    assert ca['sims'] == B * sims * moves
+    return tile[-1]
 
 
 @pytest.mark.parametrize('B', [1, 2, 3, 'wide'])
@@ -528,7 +251,7 @@ def test_tt_wide_exact_search_at_exact_ties_from_the_edge_roots(key):
     sd = {k: (torch.zeros_like(v) if k.rsplit('.', 1)[0] in last else v) for k, v in sd.items()}
     assert sum(1 for k in sd if k.rsplit('.', 1)[0] in last) == 4
     net = _wrapper(args, sd)
-    roots = _edge_roots(_edge())
+    roots = _edge_roots()
     states = [g.to_azg_state() for g in roots]
     ep = DeviceEngine(TT, len(states), seed=47)
     ep.set_states(states)
