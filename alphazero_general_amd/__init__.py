@@ -13,6 +13,16 @@ import threading as _threading
 _reference_lock = _threading.RLock()
 
 
+def __getattr__(name):
+    """`alphazero_general_amd.games` / `alphazero_general_amd.DeviceGames` -- rules on tensors of positions without a tree (games.py) --
+    resolved on first use: importing the package still loads neither torch nor the library."""
+    if name in ('games', 'DeviceGames'):
+        import importlib
+        mod = importlib.import_module(__name__ + '.games')
+        return mod if name == 'games' else mod.DeviceGames
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))
+
+
 def install():
     """Make the reference's callers use this engine unchanged: register this package's MCTS / SelfPlayAgent modules
     under the names `alphazero.MCTS` and `alphazero.SelfPlayAgent`, so that `from alphazero.MCTS import MCTS`

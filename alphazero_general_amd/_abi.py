@@ -97,6 +97,8 @@ SYMBOLS = {
     'azg_resnet_policy_value_multi_f16': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     'azg_search_f16': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i]),
     'azg_search_raw': (_i, [_vp, _vp, _f, _f32p, _i]),
+    'azg_game_step': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    'azg_game_symmetries': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'azg_policy_value_heads_f16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'azg_tower_layout': (_i, [_i, _i, _i, _vp, _vp, _vp]),
     'azg_launch_support': (_i, [_i, _i]),

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "azg_kernels.h"
+#include "azg_rules.h"
 #include "azg_conv.h"
 #include "azg_tiles.h"
 
@@ -1548,6 +1549,48 @@ extern "C" int azg_launch_support(int game, int channels) {
     // hnefatafl has device rules and no tile row: its network runs outside the library
     if (game == AZG_GAME_HNEFATAFL) return fail(AZG_E_INVALID_ARG, "no network launch is built for this game");
     return tile_support(game, channels);
+}
+
+// ---- rules without a tree (csrc/azg_rules.h): the GameState plugin on arrays of positions ---------------------------------------------
+#define RULES_SWITCH(game, CALL) \
+    switch (game) { \
+    case AZG_GAME_CONNECT4: { using G = C4; CALL; } break; \
+    case AZG_GAME_BRANDUBH: { using G = BR; CALL; } break; \
+    case AZG_GAME_TRIMOK: { using G = TM; CALL; } break; \
+    case AZG_GAME_OTHELLO: { using G = OT; CALL; } break; \
+    case AZG_GAME_GOBANG: { using G = GB; CALL; } break; \
+    case AZG_GAME_TICTACTOE: { using G = TT; CALL; } break; \
+    case AZG_GAME_HNEFATAFL: { using G = HN; CALL; } break; \
+    default: return fail(AZG_E_INVALID_ARG, "unknown game id"); }
+
+// every argument is judged here, before anything touches the device
+extern "C" int azg_game_step(void *stream, int game, int count, const azg_state *states, const int32_t *actions, azg_state *next,
+                             uint8_t *valid, uint8_t *win, void *obs, int obs_dtype, int32_t *status) {
+    if (game < 0 || game >= k_num_games) return fail(AZG_E_INVALID_ARG, "unknown game id");
+    if (count < 0) return fail(AZG_E_INVALID_ARG, "count < 0");
+    if (!states) return fail(AZG_E_INVALID_ARG, "null states_dev");
+    if (obs_dtype < 0 || obs_dtype > 2) return fail(AZG_E_INVALID_ARG, "obs_dtype must be 0 (float32), 1 (float16) or 2 (float16 NHWC8)");
+    if (actions && !status) return fail(AZG_E_INVALID_ARG, "status_dev is required when actions_dev is given");
+    if (count == 0) return AZG_OK;
+    RULES_SWITCH(game, OBS_SWITCH(obs_dtype, obs,
+        hipLaunchKernelGGL((k_game_step<G, OBS, NHWC8>), dim3(count), dim3(64), 0, (hipStream_t)stream, count, states, actions, next, valid,
+                           win, o, status)));
+    HIPCHK(hipGetLastError());
+    return AZG_OK;
+}
+
+extern "C" int azg_game_symmetries(void *stream, int game, int count, const azg_state *states, const float *pi, azg_state *sym_states,
+                                   float *sym_obs, float *sym_pi) {
+    if (game < 0 || game >= k_num_games) return fail(AZG_E_INVALID_ARG, "unknown game id");
+    if (count < 0) return fail(AZG_E_INVALID_ARG, "count < 0");
+    if (!states) return fail(AZG_E_INVALID_ARG, "null states_dev");
+    if ((pi != nullptr) != (sym_pi != nullptr)) return fail(AZG_E_INVALID_ARG, "pi_dev and sym_pi_dev go together: both or neither");
+    if (count == 0) return AZG_OK;
+    RULES_SWITCH(game,
+        hipLaunchKernelGGL((k_game_symmetries<G>), dim3(count, G::NSYM), dim3(64), 0, (hipStream_t)stream, count, states, pi, sym_states,
+                           sym_obs, sym_pi));
+    HIPCHK(hipGetLastError());
+    return AZG_OK;
 }
 
 #ifdef AZG_TREE_TIMING

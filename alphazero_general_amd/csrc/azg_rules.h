@@ -1,0 +1,82 @@
+// azg_rules.h -- the game rules of azg_games.h on plain arrays of positions, no engine and no tree: the batched form of the reference's
+// GameState plugin (alphazero/Game.py:7-113: valid_moves, play_action, win_state, observation, symmetries).  One wavefront per position
+// (k_game_step) or per (position, symmetry) (k_game_symmetries), one workgroup each, so a launch of `count` positions is a grid of `count`.
+//
+// Nothing a caller hands over becomes an address unchecked: an action is played only after it was found in the position's own move list
+// (whose entries the rule structs form from lane and cell numbers, never from cell values), every scattered index is compared with A first,
+// and every output row is addressed by the position's number alone.  A board outside the contract of azg_set_states gives a wrong answer.
+#pragma once
+#include "azg_games.h"
+
+namespace azg {
+
+// GameState.play_action (Game.py:82-85) of actions[i] on states[i] when the action is in valid_moves() -- status 1 and the position
+// unchanged otherwise, -1: no move -- then, of the position that results: the azg_state, valid_moves() (Game.py:45-47) as a 0/1 row of A
+// bytes, win_state() (Game.py:87-93) as P + 1 bytes, observation() (Game.py:96-98) in the format of k_select.  Null outputs are skipped.
+template <class G, typename OT, bool NHWC8>
+__global__ __launch_bounds__(64) void k_game_step(int count, const azg_state *states, const int32_t *actions, azg_state *next, uint8_t *valid,
+                                                  uint8_t *win, OT *obs, int32_t *status) {
+    constexpr int A = G::A, NV = G::P + 1, NCH = (G::MAXK + 63) / 64;
+    __shared__ int act_lds[NCH * 64];
+    __shared__ uint8_t mask_lds[(A + 63) / 64 * 64];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= count) return;
+    typename G::S s = G::load(&states[i], lane);
+    if (actions) {
+        const int a = __builtin_amdgcn_readfirstlane(actions[i]);
+        int st = 0;
+        if (a != -1) {
+            bool hit = false;
+            if (a >= 0 && a < A) {                                           // membership in the move list: play_action itself checks nothing
+                int my_a[NCH];
+                const int k = G::valid_list(s, lane, act_lds, my_a);
+#pragma unroll
+                for (int c = 0; c < NCH; c++) hit = hit || (c * 64 + lane < k && my_a[c] == a);
+            }
+            if (__ballot(hit) != 0) G::play(s, a); else st = 1;
+        }
+        if (status && lane == 0) status[i] = st;
+    }
+    if (next) G::store(s, &next[i], lane);                                   // (next may be states: the position is in registers)
+    if (valid) {
+        int my_a[NCH];
+        const int k = G::valid_list(s, lane, act_lds, my_a);
+        for (int e = lane; e < A; e += 64) mask_lds[e] = 0;
+        wave_sync();
+#pragma unroll
+        for (int c = 0; c < NCH; c++) if (c * 64 + lane < k && (unsigned)my_a[c] < (unsigned)A) mask_lds[my_a[c]] = 1;
+        wave_sync();
+        uint8_t *row = valid + (size_t)i * A;
+        for (int e = lane; e < A; e += 64) row[e] = mask_lds[e];
+    }
+    if (win) {
+        const int ws = G::win_bits(s);                                       // (every lane: the tafl games ballot)
+        if (lane < NV) win[(size_t)i * NV + lane] = (uint8_t)((ws >> lane) & 1);
+    }
+    if (obs) {
+        if constexpr (NHWC8) G::write_obs_nhwc8(s, (_Float16 *)obs + (size_t)i * G::CELLS * 8, lane);
+        else G::template write_obs<OT>(s, obs + (size_t)i * G::OBS, lane);
+    }
+}
+
+// GameState.symmetries(pi) (Game.py:100-113) of states[i], entry k = blockIdx.y of the reference's list: the arithmetic of k_emit_samples.
+template <class G>
+__global__ __launch_bounds__(64) void k_game_symmetries(int count, const azg_state *states, const float *pi, azg_state *sym_states,
+                                                        float *sym_obs, float *sym_pi) {
+    constexpr int A = G::A;
+    const int i = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+    if (i >= count || k >= G::NSYM) return;
+    const typename G::S s = G::load(&states[i], lane);
+    const typename G::S ss = G::symmetry(s, k);
+    const size_t o = (size_t)i * G::NSYM + k;
+    if (sym_states) G::store(ss, &sym_states[o], lane);
+    if (sym_obs) G::template write_obs<float>(ss, sym_obs + o * G::OBS, lane);
+    if (pi && sym_pi) {
+        for (int a = lane; a < A; a += 64) {
+            const int t = G::sym_action(a, k);
+            if ((unsigned)t < (unsigned)A) sym_pi[o * A + t] = pi[(size_t)i * A + a];
+        }
+    }
+}
+
+}  // namespace azg

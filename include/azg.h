@@ -414,6 +414,36 @@ int  azg_launch_support(int game, int channels);
 #define AZG_SUPPORT_SEARCH_SPARSE 4   /* ... and the sparse-heads form of the self-play launch: azg_search_wide_f16                    */
 #define AZG_SUPPORT_SEARCH_FUSED  8   /* fused heads: azg_search_f16 / azg_search_arena_f16 (and azg_resnet_policy_value*_f16)         */
 
+/* ---- rules without a tree: the GameState plugin (alphazero/Game.py:7-113) on arrays of positions ---------------------------------
+ * No engine: `game` picks the rule kernels (every azg_game), the positions are caller-owned device arrays of azg_state under the
+ * contract of azg_set_states (any board of the game's piece codes, reachable or not; a board outside it gives a wrong answer or a
+ * status, never an access outside the arrays).  One wavefront per position.  Stream-ordered, no host read, no allocation: both
+ * launches can be captured in a graph.  Every argument is judged before anything touches the device: AZG_E_INVALID_ARG for an unknown
+ * game id (as azg_game_info_get), count < 0, a null states_dev, an obs_dtype outside 0..2, actions_dev without status_dev, and pi_dev
+ * without sym_pi_dev or the reverse; count == 0 returns AZG_OK with nothing launched. */
+
+/* For position i < count: GameState.play_action(actions_dev[i]) (Game.py:82-85; connect4.pyx:65-68, brandubh/fastafl.pyx:185-189,
+ * othello.pyx:77-81, gobang.pyx:119-122, tictactoe.py:62-65, hnefatafl/fastafl.pyx:188-192; the 3-player env:
+ * alphazero_general_amd/envs/trimok.py) when that action is one of valid_moves() -- the
+ * reference's play_action checks neither validity nor win_state, so a legal move on a finished board is played -- with status_dev[i] =
+ * 0; an action that is not a legal move, or lies outside [0, A), leaves the position unchanged and status_dev[i] = 1; -1 (or
+ * actions_dev == NULL) plays nothing, status 0.  Then, of the position that results, each output whose pointer is not NULL:
+ * next_dev[i] the azg_state (may alias states_dev); valid_dev[i, 0:A] = valid_moves() as 0 / 1 bytes (Game.py:45-47); win_dev[i, 0:P+1]
+ * = win_state() (Game.py:87-93), entry j = player j won, entry P = draw; obs_dev = observation() (Game.py:96-98) as row i of the dense
+ * tensor in the formats of azg_select: obs_dtype 0 float32 [count, C, H, W], 1 float16 [count, C, H, W], 2 float16 NHWC8
+ * [count, H*W, 8]. */
+int  azg_game_step(void *stream, int game, int count, const azg_state *states_dev, const int32_t *actions_dev /*NULL: no moves*/,
+                   azg_state *next_dev, uint8_t *valid_dev /*[count, A]*/, uint8_t *win_dev /*[count, P+1]*/,
+                   void *obs_dev, int obs_dtype /*0, 1, 2 as azg_select*/, int32_t *status_dev /*[count]; required when actions_dev is given*/);
+/* GameState.symmetries(pi) (Game.py:100-113; connect4.pyx:96-99, brandubh/fastafl.pyx:213-256, othello.pyx:101-120, gobang.pyx:153-182,
+ * tictactoe.py:83-102, hnefatafl/fastafl.pyx:216-259) of every position, all num_symmetries entries in the reference's list order (the 3-player env: the position
+ * itself): sym_states_dev[i, k] the azg_state of entry k, sym_obs_dev[i, k] its observation() (float32), sym_pi_dev[i, k] its policy --
+ * pi_dev[i, a] moved to the action a maps to -- the arithmetic azg_advance applies to a finished game's samples
+ * (SelfPlayAgent.pyx:184-196).  sym_states_dev and sym_obs_dev may each be NULL; pi_dev and sym_pi_dev both or neither.  The outputs
+ * must not alias states_dev or pi_dev. */
+int  azg_game_symmetries(void *stream, int game, int count, const azg_state *states_dev, const float *pi_dev /*[count, A]*/,
+                         azg_state *sym_states_dev /*[count, NSYM]*/, float *sym_obs_dev /*[count, NSYM, C, H, W]*/, float *sym_pi_dev /*[count, NSYM, A]*/);
+
 /* ---- timing hooks for bench.py (HIP events on `stream` around the engine's own kernels) -------------------- */
 int  azg_profile_enable(azg_engine *e, int on);
 /* accumulated GPU ms + launch counts per kernel family: select, backup, advance. blocking. */
