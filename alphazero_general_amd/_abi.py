@@ -102,6 +102,7 @@ SYMBOLS = {
     'azg_policy_value_heads_f16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'azg_tower_layout': (_i, [_i, _i, _i, _vp, _vp, _vp]),
     'azg_launch_support': (_i, [_i, _i]),
+    'azg_tower_tile': (_i, [_i, _i, _i, _i, _vp]),
     'azg_resnet_tower_features_f16': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i]),
     'azg_policy_value_heads_fact_f16': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'azg_search_arena_f16': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),

@@ -45,17 +45,14 @@ struct azg_engine {
     std::vector<EvPair> pool;
 };
 
-static const azg_game_info k_info[] = {
-    // action_size, c,h,w, players, has_draw, max_turns, nsym, cells, max_children
-    {C4::A, C4::OBS_C, C4::H, C4::W, C4::P, C4::HAS_DRAW, C4::MAX_TURNS, C4::NSYM, C4::CELLS, C4::MAXK},
-    {BR::A, BR::OBS_C, BR::H, BR::W, BR::P, BR::HAS_DRAW, BR::MAX_TURNS, BR::NSYM, BR::CELLS, BR::MAXK},
-    {TM::A, TM::OBS_C, TM::H, TM::W, TM::P, TM::HAS_DRAW, TM::MAX_TURNS, TM::NSYM, TM::CELLS, TM::MAXK},
-    {OT::A, OT::OBS_C, OT::H, OT::W, OT::P, OT::HAS_DRAW, OT::MAX_TURNS, OT::NSYM, OT::CELLS, OT::MAXK},
-    {GB::A, GB::OBS_C, GB::H, GB::W, GB::P, GB::HAS_DRAW, GB::MAX_TURNS, GB::NSYM, GB::CELLS, GB::MAXK},
-    {TT::A, TT::OBS_C, TT::H, TT::W, TT::P, TT::HAS_DRAW, TT::MAX_TURNS, TT::NSYM, TT::CELLS, TT::MAXK},
-    {HN::A, HN::OBS_C, HN::H, HN::W, HN::P, HN::HAS_DRAW, HN::MAX_TURNS, HN::NSYM, HN::CELLS, HN::MAXK},
-};
-static const int k_num_games = 7;
+// the game table and everything else per game below: expanded from the one list of rule structs (AZG_GAMES, azg_games.h)
+#define AZG_GAME_INFO(G, ...) {G::A, G::OBS_C, G::H, G::W, G::P, G::HAS_DRAW, G::MAX_TURNS, G::NSYM, G::CELLS, G::MAXK},
+static const azg_game_info k_info[] = {AZG_GAMES(AZG_GAME_INFO)};   // action_size, c,h,w, players, has_draw, max_turns, nsym, cells, max_children
+#define AZG_GAME_ID(G, ...) G::ID,
+static constexpr int k_game_ids[] = {AZG_GAMES(AZG_GAME_ID)};
+static constexpr int k_num_games = sizeof(k_game_ids) / sizeof(k_game_ids[0]);
+static constexpr bool game_ids_in_order() { for (int i = 0; i < k_num_games; i++) if (k_game_ids[i] != i) return false; return true; }
+static_assert(game_ids_in_order(), "AZG_GAMES lists the rule structs in id order: each struct's ID is its position");
 
 extern "C" int azg_abi_version(void) { return AZG_ABI_VERSION; }
 #ifndef AZG_SRC_SHA
@@ -94,30 +91,16 @@ template <typename T> static int dalloc(azg_engine *e, T **p, size_t count) {
 }
 #define DALLOC(ptr, count) do { int _r = dalloc(e, &(ptr), (size_t)(count)); if (_r != AZG_OK) return _r; } while (0)
 
-// dispatch a templated kernel launch on the game id
-#define GAME_SWITCH(e, CALL) \
-    switch ((e)->cfg.game) { \
-    case AZG_GAME_CONNECT4: { using G = C4; CALL; } break; \
-    case AZG_GAME_BRANDUBH: { using G = BR; CALL; } break; \
-    case AZG_GAME_TRIMOK: { using G = TM; CALL; } break; \
-    case AZG_GAME_OTHELLO: { using G = OT; CALL; } break; \
-    case AZG_GAME_GOBANG: { using G = GB; CALL; } break; \
-    case AZG_GAME_TICTACTOE: { using G = TT; CALL; } break; \
-    case AZG_GAME_HNEFATAFL: { using G = HN; CALL; } break; \
-    default: return fail(AZG_E_UNSUPPORTED, "game has no device rules"); }
-// the same for the sparse heads (head features -> logits of the leaf's children only): not built for gobang, where nearly every
-// cell is a legal move, so a sparse row saves little and the 3616-wide feature dot products would spill, nor for tic-tac-toe, whose
-// nine logits are one output subtile either way, nor for hnefatafl, which has no network launch at all
-#define SPARSE_GAME_SWITCH(e, CALL) \
-    switch ((e)->cfg.game) { \
-    case AZG_GAME_CONNECT4: { using G = C4; CALL; } break; \
-    case AZG_GAME_BRANDUBH: { using G = BR; CALL; } break; \
-    case AZG_GAME_TRIMOK: { using G = TM; CALL; } break; \
-    case AZG_GAME_OTHELLO: { using G = OT; CALL; } break; \
-    case AZG_GAME_GOBANG: return fail(AZG_E_UNSUPPORTED, "no sparse heads for gobang (use the dense heads)"); \
-    case AZG_GAME_TICTACTOE: return fail(AZG_E_UNSUPPORTED, "no sparse heads for tic-tac-toe (use the dense heads)"); \
-    case AZG_GAME_HNEFATAFL: return fail(AZG_E_UNSUPPORTED, "no sparse heads for hnefatafl (use the dense heads)"); \
-    default: return fail(AZG_E_UNSUPPORTED, "game has no device rules"); }
+// dispatch a templated kernel launch on the game id: CALL sees the rule struct as G
+#define AZG_GAME_CASE(G_, ...) case G_::ID: { using G = G_; __VA_ARGS__; } break;
+#define GAME_SWITCH(e, ...) \
+    switch ((e)->cfg.game) { AZG_GAMES(AZG_GAME_CASE, __VA_ARGS__) default: return fail(AZG_E_UNSUPPORTED, "game has no device rules"); }
+// the same for the sparse heads (head features -> logits of the leaf's children only): the games without them (G::SPARSE_HEADS says
+// why) are refused by name
+#define AZG_SPARSE_CASE(G_, ...) case G_::ID: if constexpr (G_::SPARSE_HEADS) { using G = G_; __VA_ARGS__; } \
+    else return fail(AZG_E_UNSUPPORTED, std::string("no sparse heads for ") + G_::NAME + " (use the dense heads)"); break;
+#define SPARSE_GAME_SWITCH(e, ...) \
+    switch ((e)->cfg.game) { AZG_GAMES(AZG_SPARSE_CASE, __VA_ARGS__) default: return fail(AZG_E_UNSUPPORTED, "game has no device rules"); }
 // dispatch on the observation format the tree kernels write (obs_dtype 0: f32 planes, 1: f16 planes, 2: f16 NHWC8 rows): CALL sees the
 // element type OBS, the flag NHWC8 and the buffer as OBS *o
 #define OBS_SWITCH(obs_dtype, obs, CALL) \
@@ -985,18 +968,16 @@ static int device_cus(int *cus) {
 
 // the launch half of dispatch_tower: the row of AZG_TOWER_TILES that is (game, channels, bt, psplit, ksplit)
 static int tower_tile_launch(hipStream_t s, int game, int channels, int bt, int psplit, int ksplit, const TowerParams &P) {
-#define AZG_ROW(G, C, BT, PS, KS) \
+#define AZG_ROW(G, C, BT, PS, KS, LIMIT) \
     if (game == G::ID && channels == C && bt == BT && psplit == PS && ksplit == KS) return launch_tower<G::H, G::W, BT, C, PS, NoSearch, KS>(s, P);
     AZG_TOWER_TILES(AZG_ROW)
 #undef AZG_ROW
     return fail(AZG_E_UNSUPPORTED, "no MFMA tower for this game / channel count (azg_launch_support: the pairs with AZG_SUPPORT_TOWER)");
 }
 
-// Boards per workgroup tile: the big tile has the least MFMA padding, small ones fill the chip at small batches (the arena,
-// the single-tree API, brandubh's 512 games per GPU).  Tuning builds (hipcc -DAZG_TUNING, tools/sweep_small.py) let the
-// environment override the choice: AZG_TOWER_BOARDS, AZG_TOWER_PSPLIT; the product library reads no environment.
-// This is the policy half: it picks (boards per tile, PSPLIT, KSPLIT) among the pair's rows of AZG_TOWER_TILES (an override
-// that names no row falls to the pair's largest tile); tower_tile_launch launches the row.
+// The tile of a stand-alone tower launch: the policy is in the rows (tower_tile_pick, azg_tiles.h), in boards per CU of THIS device;
+// tower_tile_launch launches the row.  Tuning builds (hipcc -DAZG_TUNING; tools/sweep_small.py, sweep_tower.py, sweep_arena.py) let the
+// environment override the choice among the pair's rows: AZG_TOWER_BOARDS, AZG_TOWER_PSPLIT; the product library reads no environment.
 static int dispatch_tower(hipStream_t s, int game, int channels, const TowerParams &P) {
 #ifdef AZG_TUNING
     static const int forced = getenv("AZG_TOWER_BOARDS") ? atoi(getenv("AZG_TOWER_BOARDS")) : 0;
@@ -1004,49 +985,10 @@ static int dispatch_tower(hipStream_t s, int game, int channels, const TowerPara
 #else
     constexpr int forced = 0, psplit = 0;
 #endif
-    const int n = P.boards;
-    // (tile thresholds in boards per CU of THIS device -- measured on 256 CUs: 640 / 1280 boards = 2.5 / 5 per CU ... -- not in boards)
     int cus = 1;
     { const int r = device_cus(&cus); if (r != AZG_OK) return r; }
-    int bt = 0, ps = 1, ks = 1;                                      // (bt == 0: a pair without a tower -- no row matches)
-    if (game == AZG_GAME_CONNECT4 && channels == 128) {
-        bt = forced ? forced : 2 * n <= 5 * cus ? 1 : n <= 5 * cus ? 2 : 4;
-        if (bt != 1 && bt != 2) bt = 4;
-        if (psplit == 2 && bt != 4) ps = 2;                          // (an override only: the split 2-board tile exists in tuning builds alone)
-    } else if (game == AZG_GAME_CONNECT4 && channels == 64) {
-        bt = 4;
-    } else if ((game == AZG_GAME_CONNECT4 || game == AZG_GAME_OTHELLO) && channels == 32) {
-        bt = forced ? forced : n <= 4 * cus ? 2 : 4;
-        if (bt != 2) bt = 4;
-        ps = 2;
-    } else if (game == AZG_GAME_BRANDUBH && channels == 64) {
-        // measured (us per evaluation incl. heads, 256 / 512 / 1024 / 2048 boards): 1 board, no split 39 / 47 / 66 / 107;
-        // 1 board, split 35 / 46 / 80 / 113; 2 boards, split 39 / 43 / 63 / 113
-        // round 3, the k-split 1-board tile (`sp == 3`): 28 / 36 / 64 / 114 -- the shape up to 512 boards
-        bt = forced ? forced : n <= 2 * cus ? 1 : 2;
-        const int sp = psplit ? psplit : n <= 2 * cus ? 3 : n <= 4 * cus ? 2 : 1;
-        if (bt != 1) bt = 2;
-        if (bt == 1 && sp == 3) ks = 2; else if (sp == 2) ps = 2;
-    } else if (game == AZG_GAME_BRANDUBH && channels == 128) {
-        bt = 2;
-    } else if (game == AZG_GAME_TRIMOK && channels == 32) {
-        bt = forced ? forced : n <= 8 * cus ? 2 : 5;
-        const int sp = psplit ? psplit : 2;                          // (256 boards: 26 us unsplit, 23 us split in two)
-        if (bt != 2) bt = 5; else if (sp == 2 || sp == 4) ps = sp;
-    } else if (game == AZG_GAME_OTHELLO && channels == 64) {         // the k-split 1-board tile at small batches, as brandubh
-        bt = forced ? forced : n <= 2 * cus ? 1 : 2;
-        const int sp = psplit ? psplit : n <= 2 * cus ? 3 : n <= 4 * cus ? 2 : 1;
-        if (bt == 1) ks = 2; else { bt = 2; if (sp == 2) ps = 2; }
-    } else if (game == AZG_GAME_GOBANG) {                            // one board per tile, three pixel groups, at every width
-        bt = 1; ps = 3;
-    } else if (game == AZG_GAME_TICTACTOE && channels == 32) {
-        // one wavefront per workgroup in every shape: one board (one subtile, 7 spare lanes) while that fills no more than 8 wavefronts per
-        // CU, five boards (three subtiles, three border classes) up to 16 workgroups per CU, then sixteen (nine full subtiles, five border
-        // classes: 57 of 81 subtile-taps).  The thresholds are the occupancy argument alone: nothing for this game has been measured
-        bt = forced ? forced : n <= 8 * cus ? 1 : n <= 80 * cus ? 5 : 16;
-        if (bt != 1 && bt != 5) bt = 16;
-    }
-    return tower_tile_launch(s, game, channels, bt, ps, ks, P);
+    const TilePick t = tower_tile_pick(game, channels, P.boards, cus, forced, psplit);    // (bt == 0: a pair without a tower -- no row matches)
+    return tower_tile_launch(s, game, channels, t.bt, t.ps, t.ks, P);
 }
 
 // TowerParams by name: the tower's own fields; a launch then sets the heads it has, everything else stays null / 0
@@ -1151,13 +1093,16 @@ extern "C" int azg_search_f16(azg_engine *e, void *stream, const void *w, const 
     set_fused_heads(P, head_w, head_b, nullptr, nullptr, A, NV);
     SearchArgs<C4> sa{e->v, sims};
     EvPair ep; const bool prof = sims > 0 && netprof_begin((hipStream_t)stream, ep);
-    // games per workgroup like the stand-alone tower's tile (dispatch_tower): small engines -- the single-tree MCTS class, config 1's 32 games --
+    // games per workgroup: the stand-alone tower's tile for as many boards (tower_tile_pick).  Small engines -- the single-tree MCTS class, config 1's 32 games --
     // take one game per workgroup (a lone 4-board tile runs at the tower's latency for four boards: 170 us per simulation against ~60)
     int r, cus = 1;
     r = device_cus(&cus); if (r != AZG_OK) { g_kev = nullptr; return r; }
-    if (2 * e->v.B <= 5 * cus) r = launch_tower<C4::H, C4::W, 1, 128, 1, SearchArgs<C4>>((hipStream_t)stream, P, sa, sims == 0);   // sims == 0: set up only
-    else if (e->v.B <= 5 * cus) r = launch_tower<C4::H, C4::W, 2, 128, 1, SearchArgs<C4>>((hipStream_t)stream, P, sa, sims == 0);
-    else r = launch_tower<C4::H, C4::W, 4, 128, 1, SearchArgs<C4>>((hipStream_t)stream, P, sa, sims == 0);
+    switch (tower_tile_pick(AZG_GAME_CONNECT4, 128, e->v.B, cus).bt) {                                    // sims == 0: set up only
+    case 1: r = launch_tower<C4::H, C4::W, 1, 128, 1, SearchArgs<C4>>((hipStream_t)stream, P, sa, sims == 0); break;
+    case 2: r = launch_tower<C4::H, C4::W, 2, 128, 1, SearchArgs<C4>>((hipStream_t)stream, P, sa, sims == 0); break;
+    case 4: r = launch_tower<C4::H, C4::W, 4, 128, 1, SearchArgs<C4>>((hipStream_t)stream, P, sa, sims == 0); break;
+    default: r = fail(AZG_E_INTERNAL, "the fused search kernel has no tile of this many games per workgroup");
+    }
     netprof_end((hipStream_t)stream, 2, prof, ep);
     return r;
 }
@@ -1368,8 +1313,10 @@ static int search_wide(azg_engine *e, void *stream, const void *w, const float *
     if (feat_k != (hw * 16 + 31) / 32 * 32) return fail(AZG_E_INVALID_ARG, "feat_k must be H*W*16 rounded up to 32");
     if (wide_max_tile(e->cfg.game, channels) == 0)
         return fail(AZG_E_UNSUPPORTED, "persistent wide-head search: built for the pairs azg_launch_support gives AZG_SUPPORT_SEARCH_WIDE (use azg_select / network / azg_backup)");
-    if (!EXACT && e->cfg.game == AZG_GAME_GOBANG) return fail(AZG_E_UNSUPPORTED, "no sparse heads for gobang (use the exact persistent launch)");
-    if (!EXACT && e->cfg.game == AZG_GAME_TICTACTOE) return fail(AZG_E_UNSUPPORTED, "no sparse heads for tic-tac-toe (use the exact persistent launch)");
+#define AZG_NO_SPARSE(G, ...) \
+    if (!EXACT && !G::SPARSE_HEADS && e->cfg.game == G::ID) return fail(AZG_E_UNSUPPORTED, std::string("no sparse heads for ") + G::NAME + " (use the exact persistent launch)");
+    AZG_GAMES(AZG_NO_SPARSE)
+#undef AZG_NO_SPARSE
     TowerParams P = tower_params(nullptr, w, bias, pre_scale, pre_shift, e->v.B, nblocks);
     set_fact_heads(P, head1_w, head1_b, nullptr, feat_k); P.A = A; P.NV = NV;
     hipStream_t s = (hipStream_t)stream;
@@ -1542,6 +1489,16 @@ extern "C" int azg_tower_layout(int game, int boards_per_tile, int channels, int
     return r;
 }
 
+// the stand-alone tower's default tile for `boards` boards on a device of `cus` CUs: tile3 = {boards per tile, PSPLIT, KSPLIT}
+extern "C" int azg_tower_tile(int game, int channels, int boards, int cus, int32_t *tile3) {
+    if (game < 0 || game >= k_num_games) return fail(AZG_E_INVALID_ARG, "unknown game id");
+    if (boards <= 0 || cus <= 0 || !tile3) return fail(AZG_E_INVALID_ARG, "boards > 0, cus > 0, tile3 not null");
+    const TilePick t = tower_tile_pick(game, channels, boards, cus);
+    if (!t.bt) return fail(AZG_E_UNSUPPORTED, "no MFMA tower for this game / channel count (azg_launch_support: the pairs with AZG_SUPPORT_TOWER)");
+    tile3[0] = t.bt; tile3[1] = t.ps; tile3[2] = t.ks;
+    return AZG_OK;
+}
+
 extern "C" int azg_launch_support(int game, int channels) {
     if (game < 0 || game >= k_num_games) return fail(AZG_E_INVALID_ARG, "unknown game id");
     // tic-tac-toe is built for 32-channel towers only (both of its nets): any other width is refused, not answered with an empty mask
@@ -1552,16 +1509,8 @@ extern "C" int azg_launch_support(int game, int channels) {
 }
 
 // ---- rules without a tree (csrc/azg_rules.h): the GameState plugin on arrays of positions ---------------------------------------------
-#define RULES_SWITCH(game, CALL) \
-    switch (game) { \
-    case AZG_GAME_CONNECT4: { using G = C4; CALL; } break; \
-    case AZG_GAME_BRANDUBH: { using G = BR; CALL; } break; \
-    case AZG_GAME_TRIMOK: { using G = TM; CALL; } break; \
-    case AZG_GAME_OTHELLO: { using G = OT; CALL; } break; \
-    case AZG_GAME_GOBANG: { using G = GB; CALL; } break; \
-    case AZG_GAME_TICTACTOE: { using G = TT; CALL; } break; \
-    case AZG_GAME_HNEFATAFL: { using G = HN; CALL; } break; \
-    default: return fail(AZG_E_INVALID_ARG, "unknown game id"); }
+#define RULES_SWITCH(game, ...) \
+    switch (game) { AZG_GAMES(AZG_GAME_CASE, __VA_ARGS__) default: return fail(AZG_E_INVALID_ARG, "unknown game id"); }
 
 // every argument is judged here, before anything touches the device
 extern "C" int azg_game_step(void *stream, int game, int count, const azg_state *states, const int32_t *actions, azg_state *next,

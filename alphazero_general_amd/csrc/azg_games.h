@@ -18,6 +18,8 @@ namespace azg {
 // built from the ABI's int8 cells with two wave ballots.
 struct C4 {
     static constexpr int ID = AZG_GAME_CONNECT4;
+    static constexpr const char *NAME = "connect4";
+    static constexpr bool SPARSE_HEADS = true;                           // head features -> logits of the leaf's children only
     static constexpr int A = 7, H = 6, W = 7, CELLS = 42, P = 2, HAS_DRAW = 1, MAX_TURNS = 42, NSYM = 2;
     static constexpr int OBS_C = 4, OBS = OBS_C * CELLS, MAXK = 7;
     static constexpr int SYM_RAW = 0;                                    // symmetries()[SYM_RAW] is the position itself
@@ -126,6 +128,8 @@ struct C4 {
 // square"), win tests by neighbour masks.
 struct BR {
     static constexpr int ID = AZG_GAME_BRANDUBH;
+    static constexpr const char *NAME = "brandubh";
+    static constexpr bool SPARSE_HEADS = true;
     static constexpr int A = 588, H = 7, W = 7, CELLS = 49, P = 2, HAS_DRAW = 1, MAX_TURNS = 100, NSYM = 8;
     static constexpr int OBS_C = 5, OBS = OBS_C * CELLS, MAXK = 96;      // 8 attackers x 12 destinations bounds the move list
     static constexpr int SYM_RAW = 6;                                    // the identity: rot90^4 without flip (fastafl.pyx:213-256, k = 2*(4-1) + 0)
@@ -354,6 +358,8 @@ struct BR {
 // place stones in turn, three in a row wins, full board draws.  One 25-bit bitboard per player in SGPRs.
 struct TM {
     static constexpr int ID = AZG_GAME_TRIMOK;
+    static constexpr const char *NAME = "trimok";
+    static constexpr bool SPARSE_HEADS = true;
     static constexpr int A = 25, H = 5, W = 5, CELLS = 25, P = 3, HAS_DRAW = 1, MAX_TURNS = 25, NSYM = 1;
     static constexpr int OBS_C = 5, OBS = OBS_C * CELLS, MAXK = 25;
     static constexpr int SYM_RAW = 0;
@@ -436,6 +442,8 @@ struct TM {
 // ends as soon as the player to move has no legal move (win_state, othello.pyx:83-96), scored by the disc difference from the mover.
 struct OT {
     static constexpr int ID = AZG_GAME_OTHELLO;
+    static constexpr const char *NAME = "othello";
+    static constexpr bool SPARSE_HEADS = true;
     static constexpr int A = 64, H = 8, W = 8, CELLS = 64, P = 2, HAS_DRAW = 1, MAX_TURNS = 64, NSYM = 8;
     static constexpr int OBS_C = 1, OBS = OBS_C * CELLS, MAXK = 60;      // at most 60 empty squares: one wavefront holds the move list
     static constexpr int SYM_RAW = 7;                                    // the identity is the LAST entry of symmetries() (k = 2*(4-1) + 1)
@@ -560,6 +568,8 @@ struct OT {
 // row.  The observation, legal-move list and symmetries walk the cells in chunks of 64 (cell c = lane + 64 j).
 struct GB {
     static constexpr int ID = AZG_GAME_GOBANG;
+    static constexpr const char *NAME = "gobang";
+    static constexpr bool SPARSE_HEADS = false;   // nearly every cell is a legal move: a sparse row saves little and the 3616-wide feature dot products would spill
     static constexpr int A = 225, H = 15, W = 15, CELLS = 225, P = 2, HAS_DRAW = 1, MAX_TURNS = 225, NSYM = 8;
     static constexpr int OBS_C = 4, OBS = OBS_C * CELLS, MAXK = 225;     // every empty cell is legal
     static constexpr int SYM_RAW = 7;                                    // the identity is the LAST entry of symmetries(), as othello
@@ -728,6 +738,8 @@ struct GB {
 // the temperature schedule never steps, utils.py:19-23); MAX_TURNS = 9 here only sizes history, paths and the default node store.
 struct TT {
     static constexpr int ID = AZG_GAME_TICTACTOE;
+    static constexpr const char *NAME = "tic-tac-toe";
+    static constexpr bool SPARSE_HEADS = false;   // A = 9 is one output subtile, which the exact heads compute whole at the same cost
     static constexpr int A = 9, H = 3, W = 3, CELLS = 9, P = 2, HAS_DRAW = 1, MAX_TURNS = 9, NSYM = 8;
     static constexpr int OBS_C = 1, OBS = OBS_C * CELLS, MAXK = 9;
     static constexpr int SYM_RAW = 7;                                    // the identity is the LAST entry of symmetries(), as othello
@@ -826,6 +838,8 @@ struct TT {
 // by uniform reads around the moved piece; the group-surround check (cengine.pyx:204-247) as a flood fill on the masks.
 struct HN {
     static constexpr int ID = AZG_GAME_HNEFATAFL;
+    static constexpr const char *NAME = "hnefatafl";
+    static constexpr bool SPARSE_HEADS = false;   // no network launch is built for this game at all
     static constexpr int A = 2420, H = 11, W = 11, CELLS = 121, P = 2, HAS_DRAW = 1, MAX_TURNS = 512, NSYM = 8;
     // MAXK bounds the move list of ANY board azg_set_states can hand over: every move lands on a cell that holds no piece, and a cell is
     // reached by at most one mover piece from each of the four directions, so with n mover pieces k <= min(20 n, 4 (121 - n)) <= 403
@@ -1092,5 +1106,10 @@ struct HN {
         return encode(x, y, nx, ny);
     }
 };
+
+// ================================================================================================ the list
+// every game with device rules, in id order (azg_engine.hip holds each struct's ID to its place here): the game table, the switches
+// on the game id and the sparse-heads refusals are all expanded from it, so a new game is a struct above and an entry here
+#define AZG_GAMES(X, ...) X(C4, __VA_ARGS__) X(BR, __VA_ARGS__) X(TM, __VA_ARGS__) X(OT, __VA_ARGS__) X(GB, __VA_ARGS__) X(TT, __VA_ARGS__) X(HN, __VA_ARGS__)
 
 }  // namespace azg

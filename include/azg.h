@@ -414,6 +414,12 @@ int  azg_launch_support(int game, int channels);
 #define AZG_SUPPORT_SEARCH_SPARSE 4   /* ... and the sparse-heads form of the self-play launch: azg_search_wide_f16                    */
 #define AZG_SUPPORT_SEARCH_FUSED  8   /* fused heads: azg_search_f16 / azg_search_arena_f16 (and azg_resnet_policy_value*_f16)         */
 
+/* The tile a stand-alone tower launch takes by default for `boards` boards on a device of `cus` CUs: tile3 = {boards per tile, PSPLIT,
+ * KSPLIT}, the row of csrc/azg_tiles.h whose limit (in boards per CU) holds; no device needed, so tests and tooling can ask instead of
+ * restating the limits.  AZG_E_INVALID_ARG for boards <= 0, cus <= 0, a null pointer or an unknown game; AZG_E_UNSUPPORTED for a
+ * (game, channels) without AZG_SUPPORT_TOWER.  (Added within ABI v7.) */
+int  azg_tower_tile(int game, int channels, int boards, int cus, int32_t *tile3);
+
 /* ---- rules without a tree: the GameState plugin (alphazero/Game.py:7-113) on arrays of positions ---------------------------------
  * No engine: `game` picks the rule kernels (every azg_game), the positions are caller-owned device arrays of azg_state under the
  * contract of azg_set_states (any board of the game's piece codes, reachable or not; a board outside it gives a wrong answer or a

@@ -17,7 +17,6 @@ import pytest
 import torch
 
 import fixture_checks as FC
-import net_reference as R
 import test_gpu_net_fp64 as F
 import test_gpu_parity as P
 from fixture_checks import crc
@@ -25,8 +24,7 @@ from fixture_checks import crc
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 GB, DEV, A, NV = 4, 'cuda:0', 225, 3
-NETS = {'gobang_32x4': ('DEFAULT_NET_ARGS', {}), 'gobang_64x4': ('DEFAULT_NET_ARGS', dict(num_channels=64)),
-        'gobang_128x8': ('GOBANG_NET_ARGS', {})}
+NETS = ['gobang_32x4', 'gobang_64x4', 'gobang_128x8']   # test_gpu_net_fp64.GAME_NETS: reference / wrapper / check_network there
 
 
 def _game():
@@ -110,68 +108,23 @@ def test_gb_mcts_class_api_vs_reference_goldens():
 
 
 # ------------------------------------------------------------------------------------------------------------------------- network
-def _reference(key, salt=0, depth=None):
-    argname, over = NETS[key]
-    over = dict(over)
-    if depth is not None:
-        over['depth'] = depth
-    args = R.net_args(argname, **over)
-    x = torch.from_numpy(R.boards('gobang'))
-    sd, ref = R.make_state('gobang', args, 'trained', salt, probe=x)
-    return args, sd, ref, x, ref.forward(x)
-
-
-def _wrapper(args, sd, backend='hip'):
-    from alphazero_general_amd.nnet import NNetWrapper
-    net = NNetWrapper(_game(), args, device=DEV, backend=backend)
-    net.adopt(sd)
-    net.refresh()
-    assert net._hip is not None and net._hip.fact_head
-    return net
-
-
-def _check(name, args, sd, o, x, sizes):
-    net = _wrapper(args, sd)
-    hip = net._hip
-    N = x.shape[0]
-    xg = x.to(DEV)
-    for B in sizes:
-        idx = F._idx(N, B)
-        xb = xg[idx.to(DEV)].contiguous()
-        x8 = hip.to_nhwc8(xb)
-        tag = '%s_B%d' % (name, B)
-        F._stream_cmp(tag, hip, F.tower_stream(hip, x8), o, idx, 1)          # one board per tile at every batch size
-        feat = hip.forward_features_nhwc8(x8).float().cpu().reshape(B, 2, hip.feat_k)
-        assert hip.feat_k == 3616 and hip.A == A and hip.NV == NV
-        f = feat[:, :, :hip.HW * 16].reshape(B, 2, hip.HW, 16)
-        got = torch.cat([f[:, 1], f[:, 0]], 2).permute(0, 2, 1).reshape(B, 32, *o['feat'].shape[2:])
-        sel = F._sel(B)
-        rep = R.stream_report(got[sel], o['feat'][idx[sel]], tile=1)
-        F.record(dict(case=tag, what='head_features', **rep, tau=R.TAU_STREAM))
-        assert rep['ratio'] <= 1.0, (tag, rep)
-        lg = hip.forward_logits_nhwc8(x8).float().cpu()
-        F._logits_cmp(tag + '_fact', lg[:, :hip.A], lg[:, hip.A:hip.A + hip.NV], o, idx)
-        p, v = net.process(xb)
-        F._probs_cmp(tag + '_process', p.cpu(), v.cpu(), o, idx)
-
-
 @pytest.mark.parametrize('key', list(NETS))
 def test_gb_network_vs_fp64(key):
-    args, sd, ref, x, o = _reference(key)
-    _check(key, args, sd, o, x, [1, 37, 301, 2 * F._cus() + 1])
+    args, sd, ref, x, o = F.reference(key)
+    F.check_network(key, key, args, sd, ref, x, o, [1, 37, 301, 2 * F._cus() + 1])   # (one board per tile at every batch size)
 
 
 @pytest.mark.parametrize('depth', [0, 1, 2, 6])
 @pytest.mark.parametrize('key', ['gobang_32x4', 'gobang_64x4'])
 def test_gb_network_depths_vs_fp64(key, depth):
-    args, sd, ref, x, o = _reference(key, depth=depth)
-    _check('%s_depth%d' % (key, depth), args, sd, o, x, [37, 301])
+    args, sd, ref, x, o = F.reference(key, depth=depth)
+    F.check_network('%s_depth%d' % (key, depth), key, args, sd, ref, x, o, [37, 301])
 
 
 # ------------------------------------------------------------------------------------------------------------------------- search
 def _net(key, salt=7):
-    args, sd, ref, x, o = _reference(key, salt=salt)
-    return _wrapper(args, sd)
+    args, sd, ref, x, o = F.reference(key, salt=salt)
+    return F.wrapper(key, args, sd)
 
 
 @pytest.mark.parametrize('key', ['gobang_32x4', 'gobang_64x4'])
@@ -261,10 +214,10 @@ def test_gb_wide_search_deep_path():
 def _flat_net(key, salt=7):
     """the trained weights with the last Linear of both heads zeroed: every logit is 0, so every prior is the same after
     masking and every value row is uniform -- PUCT ties at every node"""
-    args, sd, ref, x, o = _reference(key, salt=salt)
+    args, sd, ref, x, o = F.reference(key, salt=salt)
     sd = {k: (torch.zeros_like(v) if k.rsplit('.', 1)[0] in ('pi_fc.4', 'v_fc.4') else v) for k, v in sd.items()}
     assert sum(1 for k in sd if k.rsplit('.', 1)[0] in ('pi_fc.4', 'v_fc.4')) == 4
-    return _wrapper(args, sd)
+    return F.wrapper(key, args, sd)
 
 
 def _sparse_draw_states(ks, per_k, seed):

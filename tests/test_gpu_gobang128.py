@@ -15,6 +15,7 @@ import torch
 import fixture_checks as FC
 import test_gpu_arena_wide as W
 import test_gpu_gobang as TG
+import test_gpu_net_fp64 as F
 
 pytestmark = pytest.mark.gpu
 GB, DEV, A = TG.GB, TG.DEV, TG.A
@@ -22,8 +23,8 @@ KEY = 'gobang_128x8'
 
 
 def _net(depth, salt=7):
-    args, sd, ref, x, o = TG._reference(KEY, salt=salt, depth=depth)
-    net = TG._wrapper(args, sd)
+    args, sd, ref, x, o = F.reference(KEY, salt=salt, depth=depth)
+    net = F.wrapper(KEY, args, sd)
     assert net._hip.CH == 128 and len(net._hip.blocks) == depth and net._hip.feat_k == 3616
     return net
 

@@ -1,5 +1,5 @@
 """Every entry point of the hand-written network kernels (csrc/azg_conv.h) against the fp64 reference of tests/net_reference.py, in logit
-space, at trained-scale weights: every (game, tower width) `dispatch_tower` supports, every tile threshold of the device (derived from its
+space, at trained-scale weights: every (game, tower width) of csrc/azg_tiles.h that a BASELINE game has, every tile threshold of the device (derived from its
 CU count), batches that are not a multiple of the tile and batches where workgroups loop over several tiles, depths 0 to BASELINE + 2,
 the collapsed wide heads with a partial chunk, the multi-model arena launch with uneven and empty splits, and the sparse heads.  The bar
 and the measure live in tests/net_reference.py (calibrated on the CPU by tests/test_net_reference_cpu.py); the measured errors go to
@@ -14,6 +14,7 @@ board in every slot of a tile) and cached for the module."""
 import ctypes as C
 import functools
 import json
+import os
 
 import numpy as np
 import pytest
@@ -24,7 +25,7 @@ import net_reference as R
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
-# (key, env, nnet args name, overrides): every (game, width) dispatch_tower supports, plus the head paths that need their own shape
+# (key, env, nnet args name, overrides): every (game, width) with tower rows of connect4, brandubh and trimok, plus the head paths that need their own shape
 NETS = {
     'connect4_128x8': ('connect4', 'CONNECT4_NET_ARGS', {}),                          # fused heads
     'connect4_64x8': ('connect4', 'CONNECT4_NET_ARGS', dict(num_channels=64)),         # collapsed wide heads (32 head channels)
@@ -34,6 +35,21 @@ NETS = {
     'brandubh_64x4_h32': ('brandubh', 'BRANDUBH_NET_ARGS', dict(value_head_channels=32, policy_head_channels=32)),   # 591 outputs: 37 subtiles
     'trimok_32x4': ('trimok', 'DEFAULT_NET_ARGS', {}),
 }
+# the nets of the games whose network tests live in their own modules (test_gpu_othello.py, test_gpu_gobang.py, test_gpu_gobang128.py,
+# test_gpu_tictactoe.py) and run through reference / wrapper / check_network here: not parametrised in this module
+GAME_NETS = {
+    'othello_64x4': ('othello', 'OTHELLO_NET_ARGS', {}),
+    'othello_32x4': ('othello', 'DEFAULT_NET_ARGS', {}),
+    'gobang_32x4': ('gobang', 'DEFAULT_NET_ARGS', {}),
+    'gobang_64x4': ('gobang', 'DEFAULT_NET_ARGS', dict(num_channels=64)),
+    'gobang_128x8': ('gobang', 'GOBANG_NET_ARGS', {}),
+    'tictactoe_32x4_h4': ('tictactoe', 'TICTACTOE_NET_ARGS', {}),          # 4 + 4 head channels, padded to 16 + 16
+    'tictactoe_32x4': ('tictactoe', 'DEFAULT_NET_ARGS', {}),
+}
+# what wrapper() and check_network() hold for those games beyond the comparisons: flags of the HipResNet, its feature row and head sizes
+HOLDS = {'othello': dict(flags=('fact_head',)),
+         'gobang': dict(flags=('fact_head',), feat_k=3616, A=225, NV=3),
+         'tictactoe': dict(flags=('fact_head', 'can_search', 'search_preferred'), feat_k=160)}
 WIDTHS = {('connect4', 128): 'connect4_128x8', ('connect4', 64): 'connect4_64x8', ('connect4', 32): 'connect4_32x4',
           ('brandubh', 64): 'brandubh_64x4', ('brandubh', 128): 'brandubh_128x4', ('trimok', 32): 'trimok_32x4'}
 
@@ -42,15 +58,34 @@ def _cus():
     return torch.cuda.get_device_properties(0).multi_processor_count
 
 
+def net_spec(key):
+    return NETS[key] if key in NETS else GAME_NETS[key]
+
+
 def tile_boards(env, ch, n, cus):
-    """boards per workgroup tile dispatch_tower (csrc/azg_engine.hip) picks for n boards"""
+    """boards per workgroup tile the stand-alone tower takes for n boards: the tests' own statement of the policy in the rows of
+    csrc/azg_tiles.h, held to the library by tests/test_tile_policy_cpu.py and, for every batch run here, by check_network"""
     if env == 'connect4' and ch == 128:
         return 1 if 2 * n <= 5 * cus else 2 if n <= 5 * cus else 4
-    if env == 'connect4':
-        return 4 if ch == 64 or n > 4 * cus else 2
-    if env == 'brandubh':
-        return 2 if ch == 128 or n > 2 * cus else 1
-    return 2 if n <= 8 * cus else 5
+    if env in ('connect4', 'othello') and ch == 32:
+        return 2 if n <= 4 * cus else 4
+    if env in ('brandubh', 'othello') and ch == 64:
+        return 1 if n <= 2 * cus else 2
+    if env == 'trimok':
+        return 2 if n <= 8 * cus else 5
+    if env == 'tictactoe':
+        return 1 if n <= 8 * cus else 5 if n <= 80 * cus else 16
+    return {('connect4', 64): 4, ('brandubh', 128): 2, ('gobang', 32): 1, ('gobang', 64): 1, ('gobang', 128): 1}[env, ch]
+
+
+def tictactoe_boards(n=301, seed=0):
+    """n boards [n, 1, 3, 3] float32 (net_reference.boards needs a turn limit to size its playouts): the empty board, all ones, all
+    minus ones, then records of tt_rules drawn without replacement -- full boards, won boards and unreachable ones among them"""
+    d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'tt_rules.npz'))
+    rng = np.random.RandomState(seed)
+    pick = rng.choice(3 ** 9, n - 3, replace=False) * 2
+    x = np.concatenate([np.zeros((1, 9)), np.ones((1, 9)), -np.ones((1, 9)), d['obs'][pick]]).astype(np.float32)
+    return x.reshape(n, 1, 3, 3)
 
 
 def batches(env, ch, cus):
@@ -66,23 +101,25 @@ def batches(env, ch, cus):
 @functools.lru_cache(maxsize=None)
 def reference(key, fill='trained', salt=0, depth=None):
     """(state_dict, Ref, boards [N, C, H, W] fp32, fp64 outputs) of one network"""
-    env, argname, over = NETS[key]
+    env, argname, over = net_spec(key)
     over = dict(over)
     if depth is not None:
         over['depth'] = depth
     args = R.net_args(argname, **over)
-    x = torch.from_numpy(R.boards(env))
+    x = torch.from_numpy(tictactoe_boards() if env == 'tictactoe' else R.boards(env))
     sd, ref = R.make_state(env, args, fill, salt, probe=x)
     return args, sd, ref, x, ref.forward(x)
 
 
 def wrapper(key, args, sd, fused=True):
     from alphazero_general_amd.nnet import NNetWrapper
-    env = NETS[key][0]
+    env = net_spec(key)[0]
     net = NNetWrapper(R.game_cls(env), args, device=DEV, backend='hip')
     net.adopt(sd)
     net.refresh()
     assert net._hip is not None
+    for flag in HOLDS.get(env, {}).get('flags', ()):
+        assert getattr(net._hip, flag), (key, flag)
     if not fused:
         net._hip.fused_head = False
     return net
@@ -145,7 +182,9 @@ def check_network(name, key, args, sd, ref, x, o, sizes, fused=True, stream=True
     """every entry point a network of this shape reaches, at every batch size in `sizes`"""
     net = wrapper(key, args, sd, fused)
     hip = net._hip
-    env = NETS[key][0]
+    env = net_spec(key)[0]
+    for k, want in HOLDS.get(env, {}).items():
+        assert k == 'flags' or getattr(hip, k) == want, (key, k, want)
     N = x.shape[0]
     xg = x.to(DEV)
     for B in sizes:
@@ -153,15 +192,19 @@ def check_network(name, key, args, sd, ref, x, o, sizes, fused=True, stream=True
         xb = xg[idx.to(DEV)].contiguous()
         x8 = hip.to_nhwc8(xb)
         tile = tile_boards(env, hip.CH, B, _cus())
+        tile3 = (C.c_int32 * 3)()
+        assert hip.L.azg_tower_tile(hip.game, int(hip.CH), int(B), _cus(), tile3) == 0 and tile3[0] == tile, (key, B, list(tile3), tile)
         tag = '%s_B%d' % (name, B)
         if stream:
             _stream_cmp(tag, hip, tower_stream(hip, x8), o, idx, tile)
         if hip.fact_head:                                      # azg_resnet_tower_features_f16: head features and their zero padding
             feat = hip.forward_features_nhwc8(x8).float().cpu().reshape(B, 2, hip.feat_k)
-            HW = hip.HW
-            assert float(feat[:, :, HW * 16:].abs().max() if hip.feat_k > HW * 16 else 0.0) == 0.0
-            f = feat[:, :, :HW * 16].reshape(B, 2, HW, 16)
-            got = torch.cat([f[:, 1], f[:, 0]], 2).permute(0, 2, 1).reshape(B, 32, *o['feat'].shape[2:])   # value channels, then policy
+            HW, vc, pc = hip.HW, ref.vc, ref.head_w.shape[0] - ref.vc
+            assert float(feat[:, :, HW * 16:].abs().max() if hip.feat_k > HW * 16 else 0.0) == 0.0     # the rows' padding behind HW x 16 features
+            f = feat[:, :, :HW * 16].reshape(B, 2, HW, 16)                                               # [B, policy | value, pos, 16]
+            assert float(f[:, 0, :, pc:].abs().max() if pc < 16 else 0.0) == 0.0                         # the padded head channels: exact zeros
+            assert float(f[:, 1, :, vc:].abs().max() if vc < 16 else 0.0) == 0.0
+            got = torch.cat([f[:, 1, :, :vc], f[:, 0, :, :pc]], 2).permute(0, 2, 1).reshape(B, vc + pc, *o['feat'].shape[2:])   # value channels, then policy
             sel = _sel(B)
             rep = R.stream_report(got[sel], o['feat'][idx[sel]], tile=1)
             record(dict(case=tag, what='head_features', **rep, tau=R.TAU_STREAM))

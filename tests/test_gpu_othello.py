@@ -25,7 +25,7 @@ import test_gpu_rules as GR
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 OT, DEV = 3, 'cuda:0'
-NETS = {'othello_64x4': ('OTHELLO_NET_ARGS', {}), 'othello_32x4': ('DEFAULT_NET_ARGS', {})}
+NETS = ['othello_64x4', 'othello_32x4']             # test_gpu_net_fp64.GAME_NETS: reference / wrapper / check_network there
 
 
 def _game():
@@ -71,79 +71,28 @@ def test_ot_mcts_class_api_vs_reference_goldens():
 
 
 # ------------------------------------------------------------------------------------------------------------------------- network
-def _reference(key, salt=0, depth=None):
-    argname, over = NETS[key]
-    over = dict(over)
-    if depth is not None:
-        over['depth'] = depth
-    args = R.net_args(argname, **over)
-    x = torch.from_numpy(R.boards('othello'))
-    sd, ref = R.make_state('othello', args, 'trained', salt, probe=x)
-    return args, sd, ref, x, ref.forward(x)
-
-
-def _wrapper(args, sd):
-    from alphazero_general_amd.nnet import NNetWrapper
-    net = NNetWrapper(_game(), args, device=DEV, backend='hip')
-    net.adopt(sd)
-    net.refresh()
-    assert net._hip is not None and net._hip.fact_head
-    return net
-
-
-def _tile(ch, n, cus):
-    """boards per workgroup tile dispatch_tower picks for othello"""
-    if ch == 32:
-        return 2 if n <= 4 * cus else 4
-    return 1 if n <= 2 * cus else 2
-
-
-def _check(name, args, sd, o, x, sizes):
-    net = _wrapper(args, sd)
-    hip = net._hip
-    N = x.shape[0]
-    xg = x.to(DEV)
-    for B in sizes:
-        idx = F._idx(N, B)
-        xb = xg[idx.to(DEV)].contiguous()
-        x8 = hip.to_nhwc8(xb)
-        tag = '%s_B%d' % (name, B)
-        F._stream_cmp(tag, hip, F.tower_stream(hip, x8), o, idx, _tile(hip.CH, B, F._cus()))
-        feat = hip.forward_features_nhwc8(x8).float().cpu().reshape(B, 2, hip.feat_k)
-        f = feat[:, :, :hip.HW * 16].reshape(B, 2, hip.HW, 16)
-        got = torch.cat([f[:, 1], f[:, 0]], 2).permute(0, 2, 1).reshape(B, 32, *o['feat'].shape[2:])
-        sel = F._sel(B)
-        rep = R.stream_report(got[sel], o['feat'][idx[sel]], tile=1)
-        F.record(dict(case=tag, what='head_features', **rep, tau=R.TAU_STREAM))
-        assert rep['ratio'] <= 1.0, (tag, rep)
-        lg = hip.forward_logits_nhwc8(x8).float().cpu()
-        F._logits_cmp(tag + '_fact', lg[:, :hip.A], lg[:, hip.A:hip.A + hip.NV], o, idx)
-        p, v = net.process(xb)
-        F._probs_cmp(tag + '_process', p.cpu(), v.cpu(), o, idx)
-
-
 @pytest.mark.parametrize('key', list(NETS))
 def test_ot_network_every_tile_vs_fp64(key):
-    args, sd, ref, x, o = _reference(key)
+    args, sd, ref, x, o = F.reference(key)
     cus = F._cus()
     th = [4 * cus] if args.num_channels == 32 else [2 * cus, 4 * cus]
-    big = _tile(args.num_channels, 1 << 30, cus)
+    big = F.tile_boards('othello', args.num_channels, 1 << 30, cus)
     sizes = sorted({1, 37, 301} | set(th) | {t + 1 for t in th} | {big * 16 * cus + 1})
-    _check(key, args, sd, o, x, sizes)
+    F.check_network(key, key, args, sd, ref, x, o, sizes)
 
 
 @pytest.mark.parametrize('depth', [0, 1, 2, 6])
 @pytest.mark.parametrize('key', list(NETS))
 def test_ot_network_depths_vs_fp64(key, depth):
-    args, sd, ref, x, o = _reference(key, depth=depth)
+    args, sd, ref, x, o = F.reference(key, depth=depth)
     cus = F._cus()
-    _check('%s_depth%d' % (key, depth), args, sd, o, x, [37, 4 * cus + 1])
+    F.check_network('%s_depth%d' % (key, depth), key, args, sd, ref, x, o, [37, 4 * cus + 1])
 
 
 # ------------------------------------------------------------------------------------------------------------------------- search launches
 def _net(key, salt=7):
-    args, sd, ref, x, o = _reference(key, salt=salt)
-    return _wrapper(args, sd)
+    args, sd, ref, x, o = F.reference(key, salt=salt)
+    return F.wrapper(key, args, sd)
 
 
 @pytest.mark.parametrize('key,B,sims,moves', [('othello_64x4', 1024, 100, 3), ('othello_32x4', 1024, 100, 3), ('othello_64x4', 96, 30, 4)])
@@ -162,11 +111,11 @@ def test_ot_wide_exact_search_at_exact_ties():
     its othello has no pass action), four slots each, against the per-phase loop on a twin engine.  Root noise and temperature off."""
     import edge_eval as ee
     from alphazero_general_amd.engine import DeviceEngine
-    args, sd, ref, x, o = _reference('othello_64x4', salt=7)
+    args, sd, ref, x, o = F.reference('othello_64x4', salt=7)
     last = ['%s.%d' % (h, max(int(k.split('.')[1]) for k in sd if k.startswith(h + '.'))) for h in ('pi_fc', 'v_fc')]
     sd = {k: (torch.zeros_like(v) if k.rsplit('.', 1)[0] in last else v) for k, v in sd.items()}
     assert sum(1 for k in sd if k.rsplit('.', 1)[0] in last) == 4 and sd[last[0] + '.weight'].shape[0] == 64
-    net = _wrapper(args, sd)
+    net = F.wrapper('othello_64x4', args, sd)
     roots = ee.roots(FC.load('ot_edge'), OT)
     ks = [int(g.valid_moves().sum()) for g in roots]
     assert {1, 2} <= set(ks) and max(ks) >= 8
@@ -199,8 +148,8 @@ def test_ot_wide_sparse_search_vs_phase_loop(key):
 def test_ot_sparse_heads_vs_fp64():
     """azg_leaf_heads_sparse_f16 on othello leaves: valid-action and value logits against the fp64 network, -inf elsewhere"""
     from alphazero_general_amd.engine import DeviceEngine
-    args, sd, ref, x, o = _reference('othello_64x4')
-    hip = _wrapper(args, sd)._hip
+    args, sd, ref, x, o = F.reference('othello_64x4')
+    hip = F.wrapper('othello_64x4', args, sd)._hip
     Game = _game()
     B = 96
     e = DeviceEngine(OT, B, seed=5, cpuct=1.25, fpu_reduction=0.2, example_capacity=1 << 16, sims_hint=8, device=0)

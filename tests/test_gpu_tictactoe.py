@@ -13,7 +13,6 @@ tests/net_reference.py:
   * azg_search_wide_exact_f16, azg_search_arena_wide_exact_f16 and azg_search_raw against the launch-per-phase loops, bit for bit;
   * the MCTS class API with pickling, the launch mask against the launches, one self-play iteration and one arena through the runners."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -29,9 +28,8 @@ import test_gpu_raw_search as RS
 import test_gpu_rules as GR
 
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 TT, DEV, A, NV = 5, 'cuda:0', 9, 3
-NETS = {'tictactoe_32x4_h4': ('TICTACTOE_NET_ARGS', {}), 'tictactoe_32x4': ('DEFAULT_NET_ARGS', {})}
+NETS = ['tictactoe_32x4_h4', 'tictactoe_32x4']       # test_gpu_net_fp64.GAME_NETS: reference / wrapper / check_network there
 
 
 def _game():
@@ -128,92 +126,29 @@ def test_tt_mcts_class_api_vs_reference_goldens_with_pickling():
 
 
 # ------------------------------------------------------------------------------------------------------------------------- network
-def boards(n=301, seed=0):
-    """n boards [n, 1, 3, 3] float32 (net_reference.boards needs a turn limit to size its playouts): the empty board, all ones, all
-    minus ones, then records of tt_rules drawn without replacement -- full boards, won boards and unreachable ones among them"""
-    d = np.load(os.path.join(G, 'tt_rules.npz'))
-    rng = np.random.RandomState(seed)
-    pick = rng.choice(3 ** 9, n - 3, replace=False) * 2
-    x = np.concatenate([np.zeros((1, 9)), np.ones((1, 9)), -np.ones((1, 9)), d['obs'][pick]]).astype(np.float32)
-    return x.reshape(n, 1, 3, 3)
-
-
-def _reference(key, salt=0, depth=None):
-    argname, over = NETS[key]
-    over = dict(over)
-    if depth is not None:
-        over['depth'] = depth
-    args = R.net_args(argname, **over)
-    x = torch.from_numpy(boards())
-    sd, ref = R.make_state('tictactoe', args, 'trained', salt, probe=x)
-    return args, sd, ref, x, ref.forward(x)
-
-
-def _wrapper(args, sd):
-    from alphazero_general_amd.nnet import NNetWrapper
-    net = NNetWrapper(_game(), args, device=DEV, backend='hip')
-    net.adopt(sd)
-    net.refresh()
-    assert net._hip is not None and net._hip.fact_head and net._hip.can_search and net._hip.search_preferred
-    return net
-
-
-def _tile(n, cus):
-    """boards per workgroup tile dispatch_tower picks for tic-tac-toe x 32"""
-    return 1 if n <= 8 * cus else 5 if n <= 80 * cus else 16
-
-
-def _check(name, args, sd, ref, o, x, sizes):
-    net = _wrapper(args, sd)
-    hip = net._hip
-    vc, pc = ref.vc, ref.head_w.shape[0] - ref.vc
-    N = x.shape[0]
-    xg = x.to(DEV)
-    for B in sizes:
-        idx = F._idx(N, B)
-        xb = xg[idx.to(DEV)].contiguous()
-        x8 = hip.to_nhwc8(xb)
-        tag = '%s_B%d' % (name, B)
-        F._stream_cmp(tag, hip, F.tower_stream(hip, x8), o, idx, _tile(B, F._cus()))
-        feat = hip.forward_features_nhwc8(x8).float().cpu().reshape(B, 2, hip.feat_k)
-        assert hip.feat_k == 160 and float(feat[:, :, 144:].abs().max()) == 0.0                  # the rows' padding behind 9 x 16 features
-        f = feat[:, :, :144].reshape(B, 2, 9, 16)                                                # [B, policy | value, pos, 16]
-        assert float(f[:, 0, :, pc:].abs().max() if pc < 16 else 0.0) == 0.0                     # the padded head channels: exact zeros
-        assert float(f[:, 1, :, vc:].abs().max() if vc < 16 else 0.0) == 0.0
-        got = torch.cat([f[:, 1, :, :vc], f[:, 0, :, :pc]], 2).permute(0, 2, 1).reshape(B, vc + pc, 3, 3)   # value channels, then policy
-        sel = F._sel(B)
-        rep = R.stream_report(got[sel], o['feat'][idx[sel]], tile=1)
-        F.record(dict(case=tag, what='head_features', **rep, tau=R.TAU_STREAM))
-        assert rep['ratio'] <= 1.0, (tag, rep)
-        lg = hip.forward_logits_nhwc8(x8).float().cpu()
-        F._logits_cmp(tag + '_fact', lg[:, :hip.A], lg[:, hip.A:hip.A + hip.NV], o, idx)
-        p, v = net.process(xb)
-        F._probs_cmp(tag + '_process', p.cpu(), v.cpu(), o, idx)
-
-
 @pytest.mark.parametrize('key', list(NETS))
 def test_tt_network_every_tile_vs_fp64(key):
     """the one-board tile at 1, 2, 16, 17, 33 boards; the five-board tile from 8 boards per CU + 1 (a ragged last tile, as + 2 ... + 5 are
     whole or ragged in turn); the sixteen-board tile from 80 per CU + 1 and at + 17, + 33 (one and two whole tiles more, ragged)"""
-    args, sd, ref, x, o = _reference(key)
+    args, sd, ref, x, o = F.reference(key)
     cus = F._cus()
     sizes = [1, 2, 16, 17, 33, 8 * cus, 8 * cus + 1, 8 * cus + 5, 8 * cus + 6, 80 * cus, 80 * cus + 1, 80 * cus + 16, 80 * cus + 17, 80 * cus + 33]
-    assert {_tile(n, cus) for n in sizes} == {1, 5, 16}
-    _check(key, args, sd, ref, o, x, sizes)
+    assert {F.tile_boards('tictactoe', 32, n, cus) for n in sizes} == {1, 5, 16}
+    F.check_network(key, key, args, sd, ref, x, o, sizes)
 
 
 @pytest.mark.parametrize('depth', [1, 6])
 @pytest.mark.parametrize('key', list(NETS))
 def test_tt_network_depths_vs_fp64(key, depth):
-    args, sd, ref, x, o = _reference(key, depth=depth)
+    args, sd, ref, x, o = F.reference(key, depth=depth)
     cus = F._cus()
-    _check('%s_depth%d' % (key, depth), args, sd, ref, o, x, [17, 8 * cus + 1, 80 * cus + 17])
+    F.check_network('%s_depth%d' % (key, depth), key, args, sd, ref, x, o, [17, 8 * cus + 1, 80 * cus + 17])
 
 
 # ------------------------------------------------------------------------------------------------------------------------- search launches
 def _net(key, salt=7):
-    args, sd, ref, x, o = _reference(key, salt=salt)
-    return _wrapper(args, sd)
+    args, sd, ref, x, o = F.reference(key, salt=salt)
+    return F.wrapper(key, args, sd)
 
 
 def _twin_search(net, B, sims, moves, states=None, **kw):
@@ -246,11 +181,11 @@ def test_tt_wide_exact_search_at_exact_ties_from_the_edge_roots(key):
     is 0, every prior the same after masking and every value row uniform -- on the roots of tt_edge.npz (one and two legal moves among
     them), against the per-phase loop on a twin engine.  Root noise and temperature off."""
     from alphazero_general_amd.engine import DeviceEngine
-    args, sd, ref, x, o = _reference(key, salt=7)
+    args, sd, ref, x, o = F.reference(key, salt=7)
     last = ['%s.%d' % (h, max(int(k.split('.')[1]) for k in sd if k.startswith(h + '.'))) for h in ('pi_fc', 'v_fc')]
     sd = {k: (torch.zeros_like(v) if k.rsplit('.', 1)[0] in last else v) for k, v in sd.items()}
     assert sum(1 for k in sd if k.rsplit('.', 1)[0] in last) == 4
-    net = _wrapper(args, sd)
+    net = F.wrapper(key, args, sd)
     roots = _edge_roots()
     states = [g.to_azg_state() for g in roots]
     ep = DeviceEngine(TT, len(states), seed=47)
@@ -265,7 +200,7 @@ def test_tt_wide_exact_search_at_exact_ties_from_the_edge_roots(key):
 
 def _tt_nets(n, key='tictactoe_32x4_h4', seed0=20):
     from alphazero_general_amd import nnet as N
-    na = R.net_args(NETS[key][0])
+    na = R.net_args(F.GAME_NETS[key][1])
     out = []
     for m in range(n):
         torch.manual_seed(seed0 + m)
