@@ -71,6 +71,8 @@ SYMBOLS = {
     'azg_leaf_heads_sparse_f16': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
     'azg_heads_softmax': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'azg_advance': (_i, [_vp, _vp, _i]),
+    'azg_advance_actions': (_i, [_vp, _vp, _vp, _i]),
+    'azg_states_dev': (_i, [_vp, C.POINTER(_vp)]),
     'azg_advance_begin': (_i, [_vp, _vp, _i, _i32p]),
     'azg_advance_commit': (_i, [_vp, _vp, _i32p]),
     'azg_root_counts': (_i, [_vp, _vp, _vp]),
@@ -98,6 +100,7 @@ SYMBOLS = {
     'azg_search_f16': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i]),
     'azg_search_raw': (_i, [_vp, _vp, _f, _f32p, _i]),
     'azg_game_step': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    'azg_game_choose': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'azg_game_symmetries': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'azg_policy_value_heads_f16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'azg_tower_layout': (_i, [_i, _i, _i, _vp, _vp, _vp]),
@@ -130,6 +133,10 @@ class AzgError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__('%s: %s' % (ERROR_NAMES.get(code, code), msg))
         self.code = code
+
+
+class AzgInvalidAction(AzgError, ValueError):
+    """AZG_E_INVALID_ACTION raised on the device: the ValueError of MCTS.update_root (MCTS.pyx:194-195), still an AzgError with its code"""
 
 
 def lib():

@@ -11,7 +11,8 @@ name `Arena` in the Coach's module to `native_arena(Arena)`, whose play_games ta
 device when every player is a model player or the reference's RawMCTSPlayer (compareToBaseline's default baselineTester, Coach.py:70,
 575-584: a raw seat, evaluated on the device with RawMCTSPlayer.process's constants) of a game with device rules.  Everything else --
 train(), gating, checkpoints, the TensorBoard writer, compareToBaseline against other non-model players (RandomPlayer, unbatched
-arenas) -- runs the reference's code; native_coach(..., raw_seats=False) sends RawMCTSPlayer arenas there too.  No agent processes, no shared
+arenas) -- runs the reference's code; native_coach(..., raw_seats=False) sends RawMCTSPlayer arenas there too, and
+native_coach(..., tree_free_seats=True) brings RandomPlayer / NNPlayer arenas, unbatched ones included, to the device.  No agent processes, no shared
 tensors, no queues: the games live on the GPU(s) (iteration.run_iteration / run_arena), the live net's weights are adopted in
 memory (NNetWrapper.adopt), and the three sample files the unchanged Coach.train loads (:442-456) are written by rank 0.
 
@@ -53,8 +54,9 @@ class _NetCache:
         return w.adopt(ref_net)
 
 
-def native_coach(Coach, *, device=None, install_arena=True, raw_seats=True):
-    """class factory: the reference's Coach with its self-play phase on the device engine (see the module docstring)"""
+def native_coach(Coach, *, device=None, install_arena=True, raw_seats=True, tree_free_seats=False):
+    """class factory: the reference's Coach with its self-play phase on the device engine (see the module docstring).  tree_free_seats:
+    native_arena's opt-in -- arenas against RandomPlayer / NNPlayer (compareToBaseline with such a baselineTester) on the device too."""
     cmod = sys.modules[Coach.__module__]
     TrainState = getattr(cmod, 'TrainState', None)
 
@@ -122,7 +124,7 @@ def native_coach(Coach, *, device=None, install_arena=True, raw_seats=True):
 
     NativeCoach.__name__ = NativeCoach.__qualname__ = 'Native' + Coach.__name__
     if install_arena and hasattr(cmod, 'Arena'):
-        cmod.Arena = native_arena(cmod.Arena, device=device, raw_seats=raw_seats)
+        cmod.Arena = native_arena(cmod.Arena, device=device, raw_seats=raw_seats, tree_free_seats=tree_free_seats)
     return NativeCoach
 
 
@@ -133,27 +135,71 @@ def is_raw_player(p):
     return t.__name__ == 'RawMCTSPlayer' and t.__module__.rsplit('.', 1)[-1] == 'GenericPlayers' and 'process' not in vars(p)
 
 
-def native_arena(Arena, *, device=None, raw_seats=True):
+def tree_free_kind(p):
+    """'random' / 'policy' for the reference's RandomPlayer / NNPlayer themselves (GenericPlayers.py:47-97; recognised like is_raw_player:
+    module and class name, no `play` of the instance's own), else None: players whose move needs no tree, played on the device by
+    games.DeviceGames.choose"""
+    t = type(p)
+    if t.__module__.rsplit('.', 1)[-1] != 'GenericPlayers' or 'play' in vars(p):
+        return None
+    return {'RandomPlayer': 'random', 'NNPlayer': 'policy'}.get(t.__name__)
+
+
+def native_arena(Arena, *, device=None, raw_seats=True, tree_free_seats=False):
     """class factory: the reference's Arena whose batched play_games runs on the device when it can (every player carries a model `.nn`
     or is a RawMCTSPlayer -- a raw seat; raw_seats=False: such arenas fall through --, Arena was built with use_batched_mcts, the game has
-    device rules); anything else falls through to the reference's own code."""
+    device rules); anything else falls through to the reference's own code.
+    tree_free_seats=True (opt-in) widens that: RandomPlayer and NNPlayer are seated too (selfplay.RANDOM_SEAT / PolicySeat) next to
+    MCTSPlayer and RawMCTSPlayer, and an Arena built with use_batched_mcts=False -- what Coach.compareToBaseline builds for a
+    RandomPlayer (Coach.py:577) -- takes the device path as well.  The MCTS seats then play with the BATCHED arena's settings
+    (args.arenaTemp, no root noise / temperature, trees re-rooted every move), not MCTSPlayer.play's own startTemp schedule and
+    args.add_root_*: INTEGRATION.md section 3a."""
     if getattr(Arena, '_azg_native', False):
-        if Arena._azg_raw_seats == raw_seats:
+        if (Arena._azg_raw_seats, Arena._azg_tree_free) == (raw_seats, tree_free_seats):
             return Arena
-        Arena = Arena._azg_base                                      # (the other raw-seat choice: wrap the reference's class afresh)
+        Arena = Arena._azg_base                                      # (another choice of seats: wrap the reference's class afresh)
 
     class NativeArena(Arena):
         _azg_native = True
-        _azg_raw_seats, _azg_base = raw_seats, Arena
+        _azg_raw_seats, _azg_tree_free, _azg_base = raw_seats, tree_free_seats, Arena
+
+        def _azg_seats(self, g):
+            """the seats of an arena with RandomPlayer / NNPlayer in it, or None: not every player is one this path accepts"""
+            from .selfplay import RANDOM_SEAT, PolicySeat
+            cache, seats = _NetCache(g, device), []
+            for p in self.players:
+                kind, nn = tree_free_kind(p), getattr(p, 'nn', None)
+                if kind == 'random':
+                    seats.append(RANDOM_SEAT)
+                elif kind == 'policy' and nn is not None:
+                    a = getattr(p, 'args', None) or {}
+                    seats.append(PolicySeat(cache.get(nn), a.get('startTemp'), a.get('temp_scaling_fn')))
+                elif raw_seats and is_raw_player(p):
+                    seats.append(None)
+                elif nn is not None and type(p).__name__ == 'MCTSPlayer':
+                    seats.append(cache.get(nn))
+                else:
+                    return None
+            if not any(s is not None and not isinstance(s, PolicySeat) and s is not RANDOM_SEAT for s in seats):
+                return None                                          # (no network searched with MCTS: the engine has nothing to do)
+            return seats
 
         def play_games(self, num, verbose=False, shuffle_players=True):          # Arena.pyx:188-376
             g = _ours(self.game_cls)
+            if tree_free_seats and g is not None and any(tree_free_kind(p) for p in self.players):
+                ours = self._azg_seats(g)
+                if ours is None:
+                    return Arena.play_games(self, num, verbose, shuffle_players)
+                return self._azg_lead(g, ours, num, shuffle_players)
             nets = [getattr(p, 'nn', None) for p in self.players]
             raw = [n is None and raw_seats and is_raw_player(p) for p, n in zip(self.players, nets)]
             if not self.use_batched_mcts or g is None or all(raw) or any(n is None and not r for n, r in zip(nets, raw)):
                 return Arena.play_games(self, num, verbose, shuffle_players)
             cache = _NetCache(g, device)
             ours = [None if r else cache.get(n) for n, r in zip(nets, raw)]     # (None: a raw seat)                      # (one wrapper per distinct reference net: [new] + [past] * (P - 1))
+            return self._azg_lead(g, ours, num, shuffle_players)
+
+        def _azg_lead(self, g, ours, num, shuffle_players):
             self.total_games = num
             r = it_mod.lead('arena', g, ours, self.args, num_games=num, details=True,
                             seats='slot' if shuffle_players else 'agent', stop=self.stop_event.is_set)

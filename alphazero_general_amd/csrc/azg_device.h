@@ -317,6 +317,54 @@ AZG_DEV float np_sum_static(const float *m, float *scr, int lane) {
     return st[0];
 }
 
+// float32 np.sum of the LDS row m[0..A) as the callers of np_sum_static need it: the sequential form below numpy's 8-element unroll
+template <int A>
+AZG_DEV float np_sum_row(const float *m, float *scr, int lane) {
+    if constexpr (A < 8) { float s = 0.f; for (int a = 0; a < A; a++) s += m[a]; return s; }
+    else return np_sum_static<A>(m, scr, lane);
+}
+
+// The temperature step two callers share: MCTS.probs (MCTS.pyx:313-321) after its counts and NNPlayer.play (GenericPlayers.py:74-80) after
+// its masked options.  x = LDS row [A] of the weights (already divided by their sum where the caller's reference does that, MCTS.pyx:320);
+// pr = LDS row [A] that receives the probabilities: temp == 0 the one-hot of the first maximum of x, otherwise x ** (1 / temp) divided by
+// its float32 np.sum.  x may be pr.  Every lane returns the sum it divided by (1 for temp == 0).
+template <int A>
+AZG_DEV float temper_probs(const float *x, float temp, float *pr, float *scr, int lane) {
+    if (temp == 0.f) {                                                       // one-hot first argmax
+        float best = x[0]; int b = 0;
+        for (int a = 1; a < A; a++) if (x[a] > best) { best = x[a]; b = a; }
+        wave_sync();                                                         // (x may be pr: every lane has read it before any lane writes)
+        for (int a = lane; a < A; a += 64) pr[a] = a == b ? 1.f : 0.f;
+        wave_sync();
+        return 1.f;
+    }
+    const double ex = 1.0 / (double)temp;
+    for (int a = lane; a < A; a += 64) pr[a] = np_pow_f32(x[a], ex);
+    wave_sync();
+    const float s2 = np_sum_row<A>(pr, scr, lane);
+    for (int a = lane; a < A; a += 64) pr[a] = pr[a] / s2;
+    wave_sync();
+    return s2;
+}
+
+// np.random.choice(A, p = pr) given its one uniform draw u (numpy's legacy choice: cdf = p.cumsum() in double, cdf /= cdf[-1],
+// searchsorted(cdf, u, side='right')): the first index whose cdf / total > u, over the LDS row pr[A].  Zero entries add nothing to a
+// cumulative sum and are skipped.  UNIFORM: every non-zero entry of pr stands for the double `each` instead of its own value (a
+// float64 p that is the same on every valid action: RandomPlayer's valids / np.sum(valids)).  Every lane returns the same action in [0, A).
+template <int A, bool UNIFORM = false>
+AZG_DEV int choice_draw(const float *pr, double u, double each = 0.0) {
+    double total = 0.0;
+    for (int a = 0; a < A; a++) { float x = pr[a]; if (x != 0.f) total += UNIFORM ? each : (double)x; }
+    double acc = 0.0; int action = 0; bool le = true;                        // cdf_i <= u  (searchsorted side='right')
+    for (int a = 0; a < A; a++) {
+        float x = pr[a];
+        if (x != 0.f) { acc += UNIFORM ? each : (double)x; le = (acc / total) <= u; }
+        if (le) action = a + 1;
+    }
+    if (action >= A) action = A - 1;
+    return action;
+}
+
 // softmax over the A policy logits of one board by one wavefront (NNetArchitecture.py:112-118, exp(log_softmax)): lane owns logits
 // lane, lane + 64, ... (A <= 1024).  pol may be global or LDS.
 // AC > 0: the row length is known at compile time, so only the ceil(AC / 64) register slots that can hold a logit are touched; the

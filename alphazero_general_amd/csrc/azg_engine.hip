@@ -394,12 +394,13 @@ extern "C" int azg_leaf_heads_sparse_f16(azg_engine *e, void *stream, const void
     return AZG_OK;
 }
 
-extern "C" int azg_advance(azg_engine *e, void *stream, int record_history) {
-    if (!e) return fail(AZG_E_INVALID_ARG, "null engine");
-    hipStream_t s = (hipStream_t)stream;
+// playMoves and what follows it, for azg_advance (actions == nullptr: k_play<G>, every move from the trees) and azg_advance_actions
+// (k_play<G, true>: the slots with an action >= 0 play it): one launch sequence, so that the two cannot drift apart
+static int advance_launches(azg_engine *e, hipStream_t s, int record_history, const int32_t *actions) {
     EvPair p; prof_begin(e, s, 2, p);
     GAME_SWITCH(e, {
-        hipLaunchKernelGGL((k_play<G>), dim3(e->v.B), dim3(64), 0, s, e->v, record_history);
+        if (actions) hipLaunchKernelGGL((k_play<G, true>), dim3(e->v.B), dim3(64), 0, s, e->v, record_history, actions);
+        else hipLaunchKernelGGL((k_play<G>), dim3(e->v.B), dim3(64), 0, s, e->v, record_history, (const int32_t *)nullptr);
         hipLaunchKernelGGL((k_finalize<G>), dim3(1), dim3(64), 0, s, e->v, (const int32_t *)nullptr);
         hipLaunchKernelGGL((k_emit_samples<G>), dim3(e->v.B, G::NSYM), dim3(64), 0, s, e->v);
         hipLaunchKernelGGL((k_emit<G>), dim3(e->v.B), dim3(64), 0, s, e->v);
@@ -410,10 +411,21 @@ extern "C" int azg_advance(azg_engine *e, void *stream, int record_history) {
     return AZG_OK;
 }
 
+extern "C" int azg_advance(azg_engine *e, void *stream, int record_history) {
+    if (!e) return fail(AZG_E_INVALID_ARG, "null engine");
+    return advance_launches(e, (hipStream_t)stream, record_history, nullptr);
+}
+
+extern "C" int azg_advance_actions(azg_engine *e, void *stream, const int32_t *actions, int record_history) {
+    if (!e) return fail(AZG_E_INVALID_ARG, "null engine");
+    if (!actions) return fail(AZG_E_INVALID_ARG, "null actions_dev");
+    return advance_launches(e, (hipStream_t)stream, record_history, actions);
+}
+
 extern "C" int azg_advance_begin(azg_engine *e, void *stream, int record_history, int32_t *fin_host) {
     if (!e || !fin_host) return fail(AZG_E_INVALID_ARG, "null argument");
     hipStream_t s = (hipStream_t)stream;
-    GAME_SWITCH(e, hipLaunchKernelGGL((k_play<G>), dim3(e->v.B), dim3(64), 0, s, e->v, record_history));
+    GAME_SWITCH(e, hipLaunchKernelGGL((k_play<G>), dim3(e->v.B), dim3(64), 0, s, e->v, record_history, (const int32_t *)nullptr));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(fin_host, e->v.fin_flag, sizeof(int32_t) * e->v.B, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -800,6 +812,12 @@ extern "C" int azg_clear_outputs(azg_engine *e, void *stream) {
 extern "C" int azg_last_actions_dev(azg_engine *e, int32_t **actions) {
     if (!e || !actions) return fail(AZG_E_INVALID_ARG, "null argument");
     *actions = e->v.last_action;
+    return AZG_OK;
+}
+
+extern "C" int azg_states_dev(azg_engine *e, const azg_state **states) {
+    if (!e || !states) return fail(AZG_E_INVALID_ARG, "null argument");
+    *states = e->v.states;
     return AZG_OK;
 }
 
@@ -1524,6 +1542,21 @@ extern "C" int azg_game_step(void *stream, int game, int count, const azg_state 
     RULES_SWITCH(game, OBS_SWITCH(obs_dtype, obs,
         hipLaunchKernelGGL((k_game_step<G, OBS, NHWC8>), dim3(count), dim3(64), 0, (hipStream_t)stream, count, states, actions, next, valid,
                            win, o, status)));
+    HIPCHK(hipGetLastError());
+    return AZG_OK;
+}
+
+extern "C" int azg_game_choose(void *stream, int game, int count, const azg_state *states, const float *policy, const float *temp,
+                               const double *u, int32_t *actions, int32_t *status) {
+    if (game < 0 || game >= k_num_games) return fail(AZG_E_INVALID_ARG, "unknown game id");
+    if (count < 0) return fail(AZG_E_INVALID_ARG, "count < 0");
+    if (!states) return fail(AZG_E_INVALID_ARG, "null states_dev");
+    if (!u) return fail(AZG_E_INVALID_ARG, "null u_dev");
+    if (!actions) return fail(AZG_E_INVALID_ARG, "null actions_dev");
+    if (!status) return fail(AZG_E_INVALID_ARG, "null status_dev");
+    if (count == 0) return AZG_OK;
+    RULES_SWITCH(game,
+        hipLaunchKernelGGL((k_game_choose<G>), dim3(count), dim3(64), 0, (hipStream_t)stream, count, states, policy, temp, u, actions, status));
     HIPCHK(hipGetLastError());
     return AZG_OK;
 }

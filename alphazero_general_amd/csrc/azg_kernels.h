@@ -925,24 +925,11 @@ AZG_DEV void root_probs(const View &ev, const Node *nodes, int root_fc, int root
     wave_sync();
     for (int i = lane; i < root_k; i += 64) cnt[nodes[root_fc + i].a] = (float)nodes[root_fc + i].n;    // counts :297-303
     wave_sync();
-    if (temp == 0.f) {                                                       // :313-317 one-hot first argmax
-        float best = cnt[0]; int b = 0;
-        for (int a = 1; a < A; a++) if (cnt[a] > best) { best = cnt[a]; b = a; }
-        for (int a = lane; a < A; a += 64) pr[a] = a == b ? 1.f : 0.f;
-        wave_sync();
-        return;
-    }
-    float s;
-    if constexpr (A < 8) { s = 0.f; for (int a = 0; a < A; a++) s += cnt[a]; }
-    else s = np_sum_static<A>(cnt, scr, lane);
-    const double ex = 1.0 / (double)temp;
-    for (int a = lane; a < A; a += 64) pr[a] = np_pow_f32(cnt[a] / s, ex);    // :320
+    if (temp == 0.f) { temper_probs<A>(cnt, temp, pr, scr, lane); return; }  // :313-317 one-hot first argmax
+    const float s = np_sum_row<A>(cnt, scr, lane);
+    for (int a = lane; a < A; a += 64) pr[a] = cnt[a] / s;                    // :320 counts / sum ...
     wave_sync();
-    float s2;
-    if constexpr (A < 8) { s2 = 0.f; for (int a = 0; a < A; a++) s2 += pr[a]; }
-    else s2 = np_sum_static<A>(pr, scr, lane);
-    for (int a = lane; a < A; a += 64) pr[a] = pr[a] / s2;                    // :321
-    wave_sync();
+    temper_probs<A>(pr, temp, pr, scr, lane);                                 // ... ** (1 / temp), :321 / np.sum
 }
 
 template <class G>
@@ -1069,8 +1056,12 @@ __global__ __launch_bounds__(64) void k_compact(View ev, int force, int first_tr
 
 // ================================================================================================ advance
 // Phase 1 (per slot): SelfPlayAgent.playMoves :156-176
-template <class G>
-__global__ __launch_bounds__(64) void k_play(View ev, int record_history) {
+// EXT (azg_advance_actions): a slot whose actions[slot] is not -1 plays THAT move instead of one sampled from its tree -- no MCTS.probs,
+// no draw (the tape counter stays), no history entry; update_root on every tree of the slot (MCTS.pyx:185-195, what Arena.pyx:170-171
+// does for the players that did not move), play_action and the end-of-game test as for any move.  A move that is not a child of the root
+// -- not legal, or outside [0, A) -- raises AZG_E_INVALID_ACTION and is NOT played: nothing a caller hands over reaches the rules unchecked.
+template <class G, bool EXT = false>
+__global__ __launch_bounds__(64) void k_play(View ev, int record_history, const int32_t *actions) {
     if (__builtin_amdgcn_readfirstlane(ev.gcount[GC_ERROR]) != 0) return;   // sticky device error: stop touching the trees
     constexpr int A = G::A;
     __shared__ float cnt[A < 8 ? 8 : A], pr[A < 8 ? 8 : A], scr[64];
@@ -1082,52 +1073,50 @@ __global__ __launch_bounds__(64) void k_play(View ev, int record_history) {
         return;                                                              // agent loop has ended by then (SelfPlayAgent.pyx:79-80)
     }
     const int tree = ev.arena ? slot * ev.T + st.player : slot;
-    HdrR hr; load_hdr(ev.hdr + tree, hr);
-    const Node *nodes = tree_nodes(ev, tree, hr.base);
-    const int fc = hr.root.fc, k = hr.root.nchild;
-    if (k > 0 && !AZG_BLOCK_OK(ev, 11, fc, k, hr.alloc)) return;
-    float temp;
-    if (ev.arena) temp = ev.arena_temp;                                      // :158
-    else { int t = st.turns < ev.temp_len ? st.turns : ev.temp_len - 1; temp = ev.temp_table[t]; }   // :156-157
-    root_probs<G>(ev, nodes, fc, k, temp, cnt, pr, scr, lane);               // :159
-    {                                                                        // no visited child: counts / 0 (:320) -- the reference
-        bool nan = false;                                                    // raises (np.seterr(all='raise'), :23); so does this
-        for (int a = lane; a < A; a += 64) nan |= pr[a] != pr[a];
-        if (__ballot(nan)) { if (lane == 0) { raise_error(ev, AZG_E_FLOATING_POINT); ev.fin_flag[slot] = 0; } return; }
-    }
-    // np.random.choice(A, p=policy) via the tape (:160): cdf in double, first index whose cdf/total > u
-    uint64_t ctr = ev.tape_ctr[slot];
-    double u;
-    if (ev.u_tape) {                                                         // the uniform np.random.choice DREW, recorded (azg_set_random_tape)
-        if (ctr >= (uint64_t)ev.perm_len) { if (lane == 0) { raise_error(ev, AZG_E_INVALID_ARG); ev.fin_flag[slot] = 0; } return; }
-        u = ev.u_tape[(size_t)slot * ev.perm_len + ctr];
-    } else u = u53(tape_u64(ev.seed, ev.slot_base + (uint64_t)slot, ctr));
-    double total = 0.0;
-    for (int a = 0; a < A; a++) { float x = pr[a]; if (x != 0.f) total += (double)x; }
-    double acc = 0.0; int action = 0; bool le = true;                        // cdf_i <= u  (searchsorted side='right')
-    for (int a = 0; a < A; a++) {
-        float x = pr[a];
-        if (x != 0.f) { acc += (double)x; le = (acc / total) <= u; }
-        if (le) action = a + 1;
-    }
-    if (action >= A) action = A - 1;
-    wave_sync();
-    if (lane == 0) { ev.tape_ctr[slot] = ctr + 1; ev.last_action[slot] = action; }
-    if (record_history && !ev.arena && ev.max_hist > 0) {                                       // :161-165 history.append((clone, probs(T=1)))
-        const int hl = __builtin_amdgcn_readfirstlane(ev.hist_len[slot]);
-        if (hl < ev.max_hist) {
-            if (temp != 1.0f) root_probs<G>(ev, nodes, fc, k, 1.0f, cnt, pr, scr, lane);
-            float *hp = ev.hist_pi + ((size_t)slot * ev.max_hist + hl) * A;
-            for (int a = lane; a < A; a += 64) hp[a] = pr[a];
-            G::store(st, &ev.hist_state[(size_t)slot * ev.max_hist + hl], lane);
-            if (lane == 0) ev.hist_len[slot] = hl + 1;
-        } else if (lane == 0) raise_error(ev, AZG_E_EXAMPLES_FULL);
-    }
-    wave_sync();
+    int action = -1;
+    if constexpr (EXT) action = __builtin_amdgcn_readfirstlane(actions[slot]);
+    const bool ext = EXT && action != -1;
+    if (!ext) {
+        HdrR hr; load_hdr(ev.hdr + tree, hr);
+        const Node *nodes = tree_nodes(ev, tree, hr.base);
+        const int fc = hr.root.fc, k = hr.root.nchild;
+        if (k > 0 && !AZG_BLOCK_OK(ev, 11, fc, k, hr.alloc)) return;
+        float temp;
+        if (ev.arena) temp = ev.arena_temp;                                      // :158
+        else { int t = st.turns < ev.temp_len ? st.turns : ev.temp_len - 1; temp = ev.temp_table[t]; }   // :156-157
+        root_probs<G>(ev, nodes, fc, k, temp, cnt, pr, scr, lane);               // :159
+        {                                                                        // no visited child: counts / 0 (:320) -- the reference
+            bool nan = false;                                                    // raises (np.seterr(all='raise'), :23); so does this
+            for (int a = lane; a < A; a += 64) nan |= pr[a] != pr[a];
+            if (__ballot(nan)) { if (lane == 0) { raise_error(ev, AZG_E_FLOATING_POINT); ev.fin_flag[slot] = 0; } return; }
+        }
+        // np.random.choice(A, p=policy) via the tape (:160): cdf in double, first index whose cdf/total > u
+        uint64_t ctr = ev.tape_ctr[slot];
+        double u;
+        if (ev.u_tape) {                                                         // the uniform np.random.choice DREW, recorded (azg_set_random_tape)
+            if (ctr >= (uint64_t)ev.perm_len) { if (lane == 0) { raise_error(ev, AZG_E_INVALID_ARG); ev.fin_flag[slot] = 0; } return; }
+            u = ev.u_tape[(size_t)slot * ev.perm_len + ctr];
+        } else u = u53(tape_u64(ev.seed, ev.slot_base + (uint64_t)slot, ctr));
+        action = choice_draw<A>(pr, u);
+        wave_sync();
+        if (lane == 0) { ev.tape_ctr[slot] = ctr + 1; ev.last_action[slot] = action; }
+        if (record_history && !ev.arena && ev.max_hist > 0) {                                       // :161-165 history.append((clone, probs(T=1)))
+            const int hl = __builtin_amdgcn_readfirstlane(ev.hist_len[slot]);
+            if (hl < ev.max_hist) {
+                if (temp != 1.0f) root_probs<G>(ev, nodes, fc, k, 1.0f, cnt, pr, scr, lane);
+                float *hp = ev.hist_pi + ((size_t)slot * ev.max_hist + hl) * A;
+                for (int a = lane; a < A; a += 64) hp[a] = pr[a];
+                G::store(st, &ev.hist_state[(size_t)slot * ev.max_hist + hl], lane);
+                if (lane == 0) ev.hist_len[slot] = hl + 1;
+            } else if (lane == 0) raise_error(ev, AZG_E_EXAMPLES_FULL);
+        }
+        wave_sync();
+    } else if (lane == 0) ev.last_action[slot] = action;
     bool ok = true;                                                          // :167-170 update_root (every tree in arena)
     if (ev.arena) { for (int t = 0; t < ev.T; t++) ok = update_root<G>(ev, slot, slot * ev.T + t, st, action, act_lds, lane) && ok; }
     else ok = update_root<G>(ev, slot, tree, st, action, act_lds, lane);
     if (!ok && lane == 0) raise_error(ev, AZG_E_INVALID_ACTION);
+    if (ext && !ok) { if (lane == 0) ev.fin_flag[slot] = 0; return; }        // (a move the rules did not produce is never played)
     G::play(st, action);                                                     // :171
     if (ev.reset_thr) {                                                      // :172-174
         const int nr = __builtin_amdgcn_readfirstlane(ev.next_reset[slot]);

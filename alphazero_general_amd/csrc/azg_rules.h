@@ -59,6 +59,46 @@ __global__ __launch_bounds__(64) void k_game_step(int count, const azg_state *st
     }
 }
 
+// The move of a player without a tree on states[i] (alphazero/GenericPlayers.py), given the uniform u[i] its np.random.choice draws:
+//   policy == NULL  RandomPlayer.play (:47-52): p = valids / np.sum(valids), uint8 / uint64 -> float64, so 1.0 / k in double on each of
+//                   the k valid actions;
+//   policy != NULL  NNPlayer.play (:69-94) on row i of policy[count, A] at temperature temp[i] (NULL: 1): options = policy * valids in
+//                   float32 (:72), then the one-hot of np.argmax (:74-77) or x ** (1 / temp) / np.sum (:79-80) -- temper_probs, the
+//                   arithmetic MCTS.probs ends with.
+// Then np.random.choice (:51, :82): choice_draw, the draw of k_play.  status 0 and the action; status 1 and action -1 where the reference
+// divides by zero or asserts: no valid move, options that sum to 0 or to no finite number, or -- outside the contract: negative or NaN
+// policy entries, u outside [0, 1) -- a draw that did not land on a valid action with a positive option.  win_state is not consulted.
+template <class G>
+__global__ __launch_bounds__(64) void k_game_choose(int count, const azg_state *states, const float *policy, const float *temp, const double *u,
+                                                    int32_t *actions, int32_t *status) {
+    constexpr int A = G::A, NCH = (G::MAXK + 63) / 64, AL = A < 8 ? 8 : A;
+    __shared__ int act_lds[NCH * 64];
+    __shared__ float opt[AL], pr[AL], scr[64];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= count) return;
+    typename G::S s = G::load(&states[i], lane);
+    int my_a[NCH];
+    const int k = G::valid_list(s, lane, act_lds, my_a);
+    for (int e = lane; e < A; e += 64) opt[e] = 0.f;
+    wave_sync();
+    const float *row = policy ? policy + (size_t)i * A : nullptr;           // (an action indexes the row and LDS only after it compared below A)
+#pragma unroll
+    for (int c = 0; c < NCH; c++)
+        if (c * 64 + lane < k && (unsigned)my_a[c] < (unsigned)A) opt[my_a[c]] = row ? row[my_a[c]] : 1.f;
+    wave_sync();
+    const double ud = u[i];
+    int action = -1;
+    if (k > 0) {
+        if (!policy) action = choice_draw<A, true>(opt, ud, 1.0 / (double)k);
+        else {
+            const float sum = temper_probs<A>(opt, temp ? temp[i] : 1.f, pr, scr, lane);
+            if (sum > 0.f && sum <= 3.402823466e38f) action = choice_draw<A>(pr, ud);   // (0, a negative sum, inf, NaN: :80 divides by it)
+        }
+        if (action >= 0 && !(opt[action] > 0.f)) action = -1;
+    }
+    if (lane == 0) { actions[i] = action; status[i] = action < 0 ? 1 : 0; }
+}
+
 // GameState.symmetries(pi) (Game.py:100-113) of states[i], entry k = blockIdx.y of the reference's list: the arithmetic of k_emit_samples.
 template <class G>
 __global__ __launch_bounds__(64) void k_game_symmetries(int count, const azg_state *states, const float *pi, azg_state *sym_states,

@@ -260,8 +260,23 @@ class DeviceEngine:
             v = v.ctypes.data_as(C.POINTER(C.c_float))
         _abi.check(self.L.azg_search_raw(self.h, _stream(), float(np.float32(policy_fill)), v, int(sims)))
 
-    def advance(self, record_history=True):
-        _abi.check(self.L.azg_advance(self.h, _stream(), int(bool(record_history))))
+    def advance(self, record_history=True, actions=None):
+        """playMoves.  actions: int32 device tensor [B] -- a slot with actions[s] >= 0 plays that move instead of one sampled from its
+        tree (azg_advance_actions: no draw, no history entry, every tree of the slot re-rooted), -1 leaves the slot to its tree.  An
+        action that is not a legal move raises the sticky AZG_E_INVALID_ACTION: counters() raises ValueError."""
+        if actions is None:
+            _abi.check(self.L.azg_advance(self.h, _stream(), int(bool(record_history))))
+            return
+        assert isinstance(actions, torch.Tensor) and actions.is_cuda and actions.device == self.device and actions.dtype == torch.int32
+        assert tuple(actions.shape) == (self.B,) and actions.is_contiguous()
+        _abi.check(self.L.azg_advance_actions(self.h, _stream(), _ptr(actions), int(bool(record_history))))
+
+    def states_dev(self):
+        """uint8 [B, 80] tensor VIEW of the root states on the device (azg_states_dev; rows as games.DeviceGames takes them): it
+        follows the engine, and dies with it"""
+        p = C.c_void_p()
+        _abi.check(self.L.azg_states_dev(self.h, C.byref(p)))
+        return torch.as_tensor(_DevArray(p.value, (self.B, C.sizeof(_abi.State)), '|u1'), device=self.device)
 
     def advance_begin(self, record_history=True):
         """playMoves up to the win test; returns fin[B] (winstate bits, 0 = still running).  Finished slots keep their
@@ -352,6 +367,9 @@ class DeviceEngine:
         if c.error == _abi.E_FLOATING_POINT:                              # what numpy raises in the reference (MCTS.pyx:23,320)
             raise FloatingPointError('invalid value encountered in divide: playMoves at a root without a visited child (numMCTSSims < 2) '
                                      'or a policy whose valid entries sum to 0')
+        if c.error == _abi.E_INVALID_ACTION:                              # what MCTS.update_root raises (MCTS.pyx:194-195)
+            raise _abi.AzgInvalidAction(c.error, 'Invalid action encountered while updating root (raised on device: advance with an action '
+                                                 'that is not a legal move)')
         if c.error:
             raise _abi.AzgError(c.error, 'raised on device (tree arena or example buffer overflow / invalid action)')
         return dict(sims=c.sims, expansions=c.expansions, games_played=c.games_played, num_results=c.num_results,

@@ -4,8 +4,8 @@ azg_game_symmetries (include/azg.h).  What it is for: evaluating a net on a batc
 GenericPlayers.py:55-97), expanding stored (state, pi) samples into their symmetries at training time, writing another search.
 
 A position is one row of a uint8 tensor [n, 80]: the bytes of an azg_state.  `pack` / `unpack` / `to_games` convert from and to host
-objects (this package's envs, the reference's own classes, or (cells, player, turns[, aux0]) tuples); `step` and `symmetries` are one
-kernel launch each on torch's current stream, read nothing back and, given `out=`, allocate nothing -- so a play loop can be captured
+objects (this package's envs, the reference's own classes, or (cells, player, turns[, aux0]) tuples); `step`, `symmetries` and `choose`
+(the move of a player without a tree: RandomPlayer, NNPlayer) are one kernel launch each on torch's current stream, read nothing back and, given `out=`, allocate nothing -- so a play loop can be captured
 in a graph.  There is no CPU path for the rules themselves: `step` / `symmetries` need a HIP device."""
 import collections
 import ctypes as C
@@ -19,6 +19,7 @@ from .Game import azg_game_id
 STATE_BYTES = C.sizeof(_abi.State)                              # 80
 Step = collections.namedtuple('Step', 'next valid win obs status')
 Symmetries = collections.namedtuple('Symmetries', 'states obs pi')
+Choice = collections.namedtuple('Choice', 'actions status')
 _OBS_FORMS = {torch.float32: 0, torch.float16: 1, 'nhwc8': 2}
 
 
@@ -106,7 +107,7 @@ class DeviceGames:
         c, h, w = self.obs_shape
         return (h * w, 8) if form == 'nhwc8' else (c, h, w)
 
-    # ---- the two launches ---------------------------------------------------------------------------------------
+    # ---- the launches ---------------------------------------------------------------------------------------
     def step(self, states, actions=None, *, next=True, valid=True, win=True, obs=None, out=None):
         """play actions[i] on states[i] where it is legal (GameState.play_action; an illegal or out-of-range action leaves the position
         as it is and sets status 1; -1 or actions=None: no move), then of the resulting positions return a Step record:
@@ -149,3 +150,32 @@ class DeviceGames:
         with torch.cuda.device(self.device):
             _abi.check(self.L.azg_game_symmetries(_stream(), self.game, n, _ptr(states), _ptr(pi), _ptr(b_states), _ptr(b_obs), _ptr(b_pi)))
         return Symmetries(*[None if b is None else b[:n] for b in (b_states, b_obs, b_pi)])
+
+    def choose(self, states, policy=None, temp=None, u=None, out=None):
+        """the move of a player without a tree on every position (azg_game_choose), as a Choice record (actions int32 [n], status int32 [n]):
+          policy=None          RandomPlayer.play (GenericPlayers.py:47-52): uniform over the valid moves
+          policy float32 [n, A] NNPlayer.play (:69-94) with row i as the network's policy: masked, raised to 1 / temp[i] (temp float32 [n];
+                               None: 1; an entry 0: the first maximum), normalised
+        then np.random.choice given u[i], float64 [n] in [0, 1), the uniform that call draws; u=None draws torch.rand on the device.
+        status 1 with action -1 where the reference would divide by zero (no valid move, options that sum to 0); returned, never raised.
+        out: a Choice whose tensors are written instead of new ones (they may hold more than n rows)."""
+        states = self._rows(states)
+        n = states.shape[0]
+        o = out if out is not None else Choice(None, None)
+        if policy is not None:
+            assert isinstance(policy, torch.Tensor) and policy.dtype == torch.float32 and policy.device == self.device, 'policy: float32 on the device'
+            assert tuple(policy.shape) == (n, self.A) and policy.is_contiguous(), 'policy: contiguous [n, A]'
+        if temp is not None:
+            assert policy is not None, 'temp goes with a policy (RandomPlayer has no temperature)'
+            assert isinstance(temp, torch.Tensor) and temp.dtype == torch.float32 and temp.device == self.device, 'temp: float32 on the device'
+            assert tuple(temp.shape) == (n,) and temp.is_contiguous(), 'temp: contiguous [n]'
+        if u is None:
+            u = torch.rand(n, dtype=torch.float64, device=self.device)
+        assert isinstance(u, torch.Tensor) and u.dtype == torch.float64 and u.device == self.device, 'u: float64 on the device'
+        assert tuple(u.shape) == (n,) and u.is_contiguous(), 'u: contiguous [n]'
+        b_actions = self._buf(o.actions, True, 'actions', n, (), torch.int32)
+        b_status = self._buf(o.status, True, 'status', n, (), torch.int32)
+        with torch.cuda.device(self.device):
+            _abi.check(self.L.azg_game_choose(_stream(), self.game, n, _ptr(states), _ptr(policy), _ptr(temp), _ptr(u), _ptr(b_actions),
+                                              _ptr(b_status)))
+        return Choice(b_actions[:n], b_status[:n])

@@ -321,14 +321,20 @@ def lead(op, game_cls, nnets, args, *, iteration=0, folder=None, num_games=None,
         if op == 'stop':
             D.broadcast_object({'op': 'stop'}, group=group)
             return None
-        uniq, index = [], []                                         # (gating: [new] + [past] * (P - 1) -- every distinct net travels once)
-        for n in nnets:
+        from .selfplay import PolicySeat, is_tree_free
+        uniq, index, seats = [], [], []                              # (gating: [new] + [past] * (P - 1) -- every distinct net travels once)
+        for seat in nnets:
+            # a tree-free seat (selfplay.RANDOM_SEAT, PolicySeat) travels with the command: RANDOM_SEAT as it is, a PolicySeat as its start
+            # temperature and iterated schedule, its network with the weights like any other
+            n = seat.net if isinstance(seat, PolicySeat) else None if is_tree_free(seat) else seat
+            seats.append(PolicySeat(None, seat.start_temp, None, seat.table(game_cls, args).tolist()) if isinstance(seat, PolicySeat)
+                         else seat if is_tree_free(seat) else None)
             j = -1 if n is None else next((j for j, m in enumerate(uniq) if m is n), None)     # (None: a warm-up iteration plays without a net)
             if j is None:
                 j = len(uniq); uniq.append(n)
             index.append(j)
         cmd = {'op': op, 'args': portable_args(args, game_cls), 'iteration': int(iteration), 'num_games': num_games, 'kw': kw,
-               'index': index, 'net_args': [{k: n.args[k] for k in DEFAULT_NET_ARGS if k in n.args} for n in uniq], 'meta': [D.state_dict_meta(n.nnet.state_dict()) for n in uniq]}
+               'index': index, 'seats': seats, 'net_args': [{k: n.args[k] for k in DEFAULT_NET_ARGS if k in n.args} for n in uniq], 'meta': [D.state_dict_meta(n.nnet.state_dict()) for n in uniq]}
         D.broadcast_object(cmd, group=group)
         for n, m in zip(uniq, cmd['meta']):
             D.broadcast_state_dict(n.nnet.state_dict(), m, group=group)
@@ -353,6 +359,12 @@ def serve(game_cls, device=None, group=None):
         args = dotdict(cmd['args'])
         uniq = [_net_from(game_cls, D.broadcast_state_dict(None, m, group=group), na, dev) for na, m in zip(cmd['net_args'], cmd['meta'])]
         nnets = [uniq[j] if j >= 0 else None for j in cmd['index']]
+        from .selfplay import PolicySeat
+        for i, seat in enumerate(cmd.get('seats') or []):            # tree-free seats: RANDOM_SEAT as sent, a PolicySeat around its network
+            if isinstance(seat, PolicySeat):
+                nnets[i] = PolicySeat(nnets[i], seat.start_temp, None, seat.temp_table)
+            elif seat is not None:
+                nnets[i] = seat
         if cmd['op'] == 'selfplay':
             run_iteration(game_cls, nnets[0], args, cmd['iteration'], None, group=group, **dict(cmd['kw'], keep_samples=False))
         else:

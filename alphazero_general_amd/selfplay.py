@@ -14,13 +14,59 @@ from . import _abi
 from .engine import DeviceEngine
 from .nnet import HipResNet
 from .Game import azg_game_id
-from .utils import AGENT_STREAM, default_temp_scaling, raw_launch_default
+from .utils import AGENT_STREAM, TREEFREE_SEED_XOR, TREEFREE_STREAM, default_temp_scaling, raw_launch_default, seat_temp_table
 
 
 # The persistent launch of a wide-head network hands the tree NNetWrapper.process's own bits by default ('exact': visit counts and pi
 # bit-exact against the reference's evaluation, BASELINE north_star); 'sparse' (the logits of the valid actions only: equal to rounding,
 # 10-35 % faster by shard size) is the opt-in: SelfPlayRunner(search_heads='sparse')
 SEARCH_HEADS_DEFAULT = 'exact'
+
+
+class _RandomSeat:
+    """an arena seat that plays RandomPlayer.play (alphazero/GenericPlayers.py:47-52): no network, no tree"""
+
+    def __repr__(self):
+        return 'RANDOM_SEAT'
+
+    def __reduce__(self):                                            # (one object per process: `is RANDOM_SEAT` holds after pickling)
+        return (_random_seat, ())
+
+    def __eq__(self, other):
+        return isinstance(other, _RandomSeat)
+
+    def __hash__(self):
+        return hash('RANDOM_SEAT')
+
+
+def _random_seat():
+    return RANDOM_SEAT
+
+
+RANDOM_SEAT = _RandomSeat()
+
+
+class PolicySeat:
+    """an arena seat that plays NNPlayer.play (GenericPlayers.py:55-97): one evaluation of `net` per move, masked, raised to
+    1 / temperature and sampled -- no tree.  start_temp / temp_scaling_fn: the player's args.startTemp and args.temp_scaling_fn (:59, :73;
+    None: the arena's own args).  temp_table: the schedule already iterated, [num_players][turns] (utils.seat_temp_table) -- how a callable
+    that does not pickle travels to serving ranks (iteration.lead)."""
+
+    def __init__(self, net, start_temp=None, temp_scaling_fn=None, temp_table=None):
+        self.net, self.start_temp, self.temp_scaling_fn, self.temp_table = net, start_temp, temp_scaling_fn, temp_table
+
+    def table(self, game_cls, args):
+        """[P, turns] float32: the temperature of this seat's move at turn t when it sits as player p"""
+        from .Game import schedule_turns
+        if self.temp_table is not None:
+            return np.ascontiguousarray(self.temp_table, np.float32)
+        fn = self.temp_scaling_fn or args.get('temp_scaling_fn', default_temp_scaling)
+        t0 = args.get('startTemp', 1.0) if self.start_temp is None else self.start_temp
+        return seat_temp_table(fn, t0, game_cls.max_turns(), game_cls.num_players(), schedule_turns(game_cls))
+
+
+def is_tree_free(seat):
+    return isinstance(seat, (_RandomSeat, PolicySeat))
 
 
 class _Lane:
@@ -335,6 +381,11 @@ class ArenaRunner:
     (wins, draws, winrates) contract of Arena.play_games (:376) via get_game_results semantics (utils.py:34-54).
     A None entry of `nnets` is a raw seat: the batched evaluation of the reference's RawMCTSPlayer.process (GenericPlayers.py:198-200),
     policy float32(1 / A) for every action and value zeros.
+    RANDOM_SEAT or a PolicySeat entry is a tree-free seat (RandomPlayer / NNPlayer, GenericPlayers.py:47-97): the search sees it as a raw
+    seat and its tree is ignored; after the search DeviceGames.choose picks its move from the root states and advance(actions=...) plays
+    it, re-rooting every tree of the game as Arena.pyx:170-171 does with player.update.  Its np.random.choice uniform is
+    u53(tape(seed ^ TREEFREE_SEED_XOR, TREEFREE_STREAM + global slot, round)): independent of how the games are sharded.  Rounds with
+    tree-free seats run eagerly (use_graph is ignored).
 
     A move runs as ONE persistent launch where one exists (fused_search=None picks it, True insists on it): azg_search_arena_wide_exact_f16
     when every network has factorised heads the persistent search supports (raw seats included), azg_search_arena_f16 for connect4 x 128
@@ -342,13 +393,15 @@ class ArenaRunner:
 
     def __init__(self, game_cls, nnets, args, *, num_slots, seed=0, slot_base=0, device=None, use_graph=True, result_capacity=None,
                  seats='agent', nodes_per_tree=0, fused_search=None):
-        self.game_cls, self.nnets, self.args = game_cls, list(nnets), args
+        self.game_cls, self.seats_given, self.args = game_cls, list(nnets), args
+        self.tree_free = [is_tree_free(n) for n in self.seats_given]
+        self.nnets = [None if tf else n for n, tf in zip(self.seats_given, self.tree_free)]   # (the search: a tree-free seat is a raw seat)
         self.game = azg_game_id(game_cls)
         self.B = int(num_slots)
         P = game_cls.num_players()
         assert len(self.nnets) == P
         self.real = [n for n in self.nnets if n is not None]
-        assert self.real, 'an arena needs at least one network'
+        assert self.real, 'an arena needs at least one network searched with MCTS'
         self.raw_seats = len(self.real) < P
         self.seed, self.slot_base = int(seed), int(slot_base)
         # seat permutation, one per agent, drawn from the agent-level tape stream (SelfPlayAgent.pyx:44-47)
@@ -404,8 +457,71 @@ class ArenaRunner:
         self.wide_search = can_wide and (bool(fused_search) or (fused_search is None and all(n._hip.search_preferred for n in self.real)))
         self.fused_search = can if fused_search is None else bool(fused_search) and can
         self._graph = None
-        if (self.device_split or self.wide_search) and use_graph:
+        self.rounds = 0
+        if any(self.tree_free):
+            self._init_tree_free()
+        elif (self.device_split or self.wide_search) and use_graph:
             self.capture()
+
+    # ---- tree-free seats (RandomPlayer / NNPlayer) ------------------------------------------------------------------------------
+    def _init_tree_free(self):
+        from .games import DeviceGames
+        e, P, args = self.engine, self.game_cls.num_players(), self.args
+        self.games = DeviceGames(self.game_cls, device=e.device)
+        perms = self.slot_player_to_index if self.slot_seats is not None else [self.player_to_index] * self.B
+        dev = lambda rows, dt: torch.tensor(np.asarray(rows), dtype=dt, device=e.device)
+        self._tf_seat = dev([[m[p] for p in range(P)] for m in perms], torch.int64)                      # [B, P] player -> seat
+        self._tf_random = [mi for mi, seat in enumerate(self.seats_given) if isinstance(seat, _RandomSeat)]
+        self._tf_u = torch.zeros(self.B, dtype=torch.float64, device=e.device)
+        self._tf_none = torch.full((self.B,), -1, dtype=torch.int32, device=e.device)
+        self._tf_policy = []                                         # (seat index, net, temperature table [P, turns] on the device)
+        for mi, seat in enumerate(self.seats_given):
+            if isinstance(seat, PolicySeat):
+                self._tf_policy.append((mi, seat.net, dev(seat.table(self.game_cls, args), torch.float32)))
+
+    def _tree_free_uniforms(self):
+        """the np.random.choice uniform of every slot for this round, keyed by the GLOBAL slot id and the round"""
+        L, seed = _abi.lib(), (self.seed ^ TREEFREE_SEED_XOR) & 0xFFFFFFFFFFFFFFFF
+        base = TREEFREE_STREAM + self.slot_base
+        u = np.array([(L.azg_tape_u64(seed, base + s, self.rounds) >> 11) * (1.0 / 9007199254740992.0) for s in range(self.B)], np.float64)
+        self._tf_u.copy_(torch.from_numpy(u))
+        return self._tf_u
+
+    def _seat_policy(self, net, states):
+        """NNPlayer.play :70: the seat's network on the root position of all B slots -> policy [B, A] float32"""
+        hip = getattr(net, '_hip', None)
+        if hip is None and hasattr(net, 'refresh') and getattr(net, '_infer', None) is None:
+            net.refresh(); hip = getattr(net, '_hip', None)
+        if hip is not None:
+            x = self.games.step(states, None, next=False, valid=False, win=False, obs='nhwc8').obs
+            return hip.forward_nhwc8(x, key=200)[0].contiguous()
+        x = self.games.step(states, None, next=False, valid=False, win=False, obs=torch.float16).obs
+        return net.process(x)[0].contiguous()
+
+    def _advance_tree_free(self):
+        """the end of a round with tree-free seats: their moves from DeviceGames.choose, everybody else's from the trees"""
+        e = self.engine
+        states = e.states_dev()
+        words = states[:, 64:72].view(torch.int32)                   # azg_state.player, .turns
+        mover, turns = words[:, 0].long(), words[:, 1].long()
+        seat = self._tf_seat.gather(1, mover[:, None])[:, 0]
+        u = self._tree_free_uniforms()
+        actions = self._tf_none
+        # (a mover without a move to choose -- status 1: the reference divides by zero there -- gets -2, which advance refuses with the
+        #  sticky AZG_E_INVALID_ACTION; a finished game that idles is never asked for its action)
+        pick = lambda c: torch.where(c.status == 0, c.actions, torch.full_like(c.actions, -2))
+        if self._tf_random:
+            c = self.games.choose(states, u=u)
+            israndom = torch.zeros_like(seat, dtype=torch.bool)
+            for mi in self._tf_random:
+                israndom |= seat == mi
+            actions = torch.where(israndom, pick(c), actions)
+        for mi, net, tab in self._tf_policy:
+            temp = tab[mover.clamp(0, tab.shape[0] - 1), turns.clamp(0, tab.shape[1] - 1)].contiguous()
+            c = self.games.choose(states, self._seat_policy(net, states), temp, u)
+            actions = torch.where(seat == mi, pick(c), actions)
+        e.advance(False, actions.contiguous())
+        self.rounds += 1
 
     def _rows(self):
         e = self.engine
@@ -484,6 +600,15 @@ class ArenaRunner:
         self._graph = g
 
     def play_round(self, eager=False):
+        if any(self.tree_free):                                      # eager: search (the tree-free seats as raw seats), choose, advance
+            sims = int(self.args.get('numMCTSSims', 100))
+            if self.wide_search:
+                self._search_wide(sims)
+            else:
+                for _ in range(sims):
+                    self.step()
+            self._advance_tree_free()
+            return
         if self.wide_search or (self.device_split and (self._graph is not None or self.fused_search)):
             if eager or self._graph is None:
                 self._round_device_split(int(self.args.get('numMCTSSims', 100)))

@@ -47,7 +47,25 @@ def temp_table(temp_fn, start_temp, max_turns, turns=None):
     return np.asarray(out, dtype=np.float32)
 
 
+def seat_temp_table(temp_fn, start_temp, max_turns, num_players, turns=None):
+    """temp[p][t]: the temperature a PLAYER object seated as player p uses for a move it makes at turn t (NNPlayer.play,
+    GenericPlayers.py:73: self.temp = temp_scaling_fn(self.temp, state.turns, max_turns) on ITS OWN moves only, from args.startTemp) --
+    player p moves at the turns t with t % num_players == p; the entries of the other turns hold the value the player carries then.
+    `max_turns` / `turns` as temp_table."""
+    n = max(int(turns or max_turns or 0), 1) + 2
+    out = np.zeros((int(num_players), n), np.float32)
+    for p in range(int(num_players)):
+        t = float(start_temp)
+        for turn in range(n):
+            if turn % int(num_players) == p:
+                t = temp_fn(t, turn, max_turns)
+            out[p, turn] = t
+    return out
+
+
 AGENT_STREAM = 0x4000000000000000   # tape stream of agent-level draws (fast coin, seat shuffle); DESIGN.md
+TREEFREE_STREAM = 0x2000000000000000   # ... of the np.random.choice uniforms of tree-free arena seats: + global slot id, counter = round
+TREEFREE_SEED_XOR = 0x7F4EE5EA7
 
 
 # Searches that use no network -- MCTS.raw_search (RawMCTSPlayer) and the rounds of a warm-up agent -- can run their whole simulation

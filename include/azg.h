@@ -207,6 +207,18 @@ int  azg_advance(azg_engine *e, void *stream, int record_history);
 int  azg_advance_begin(azg_engine *e, void *stream, int record_history, int32_t *fin_host);
 int  azg_advance_commit(azg_engine *e, void *stream, const int32_t *counted_host);
 
+/* azg_advance with moves the trees did not choose (within ABI v7): a slot with actions_dev[s] >= 0 plays THAT action, as Arena.pyx:139-186
+ * plays the move of a player without a tree (RandomPlayer, NNPlayer: alphazero/GenericPlayers.py:47-97) and tells the MCTS players with
+ * player.update(state, action) (:170-171, MCTSPlayer.update -> MCTS.update_root, GenericPlayers.py:127-128).  For such a slot: no
+ * MCTS.probs and no draw from the slot's tape (its counter stays, unless an unexpanded root has its children added and shuffled first,
+ * MCTS.pyx:186-187); no history entry; update_root on EVERY tree of the slot; play_action, the end-of-game test, results, samples, reset
+ * and compaction as for any move.  An action that is not a legal move of the slot's position (or lies outside [0, A), -1 apart) raises the
+ * sticky AZG_E_INVALID_ACTION and is not played.  A slot with actions_dev[s] == -1 does exactly what azg_advance does.  actions_dev:
+ * device int32 [num_slots], read by the launch (stream-ordered).  Arena and self-play engines. */
+int  azg_advance_actions(azg_engine *e, void *stream, const int32_t *actions_dev /*[B]*/, int record_history);
+/* device view of the B root states (azg_state [num_slots]), like azg_last_actions_dev: what the next azg_select starts from */
+int  azg_states_dev(azg_engine *e, const azg_state **states_dev);
+
 /* ---- single-tree API (MCTS.pyx public methods; slot-wise) ------------------------------------------------ */
 int  azg_root_counts(azg_engine *e, void *stream, int32_t *counts_dev /*[B, A]*/);                 /* MCTS.counts :297-303 */
 int  azg_root_probs(azg_engine *e, void *stream, float temp, float *probs_dev /*[B, A]*/);        /* MCTS.probs  :308-329 */
@@ -449,6 +461,24 @@ int  azg_game_step(void *stream, int game, int count, const azg_state *states_de
  * must not alias states_dev or pi_dev. */
 int  azg_game_symmetries(void *stream, int game, int count, const azg_state *states_dev, const float *pi_dev /*[count, A]*/,
                          azg_state *sym_states_dev /*[count, NSYM]*/, float *sym_obs_dev /*[count, NSYM, C, H, W]*/, float *sym_pi_dev /*[count, NSYM, A]*/);
+
+/* The move of a player WITHOUT a tree on every position (alphazero/GenericPlayers.py; within ABI v7), one wavefront per position, under
+ * the contract of azg_game_step: every argument judged first (AZG_E_INVALID_ARG for an unknown game, count < 0, a null states_dev / u_dev
+ * / actions_dev / status_dev; count == 0: AZG_OK, nothing launched), stream-ordered, no host read, no allocation.
+ *   policy_dev == NULL  RandomPlayer.play (:47-52): p = valids / np.sum(valids) -- uint8 / uint64, so float64 1.0 / k on the k valid moves;
+ *   policy_dev != NULL  NNPlayer.play (:69-94) with row i of policy_dev as nn.predict's policy: options = policy * valids (float32, :72);
+ *                       temp_dev[i] == 0: the one-hot of np.argmax(options) (:74-77); otherwise x ** (1 / temp) in numpy's float32 pow,
+ *                       divided by its float32 pairwise np.sum (:79-80) -- the arithmetic MCTS.probs ends with (MCTS.pyx:313-321).
+ * Then np.random.choice(A, p = probs) (:51, :82) given u_dev[i], the uniform in [0, 1) that call draws: the double cumulative sum
+ * normalised by its total, first index above u (searchsorted side='right') -- what azg_advance does with its own draw.  status_dev[i] =
+ * 0 and actions_dev[i] the move; status 1 and action -1 where the reference divides by zero or fails its assertion (:86-92): no valid
+ * move, or options that sum to 0 or to no finite number.  Negative or NaN policy entries and a u outside [0, 1) are outside the
+ * contract: they give a valid action or status 1, never an access outside the arrays.  win_state is not consulted (the players do not). */
+int  azg_game_choose(void *stream, int game, int count, const azg_state *states_dev,
+                     const float *policy_dev /*[count, A] probabilities, or NULL: RandomPlayer*/,
+                     const float *temp_dev   /*[count], or NULL: temperature 1*/,
+                     const double *u_dev     /*[count], the uniform np.random.choice draws, in [0, 1)*/,
+                     int32_t *actions_dev    /*[count]*/, int32_t *status_dev /*[count]*/);
 
 /* ---- timing hooks for bench.py (HIP events on `stream` around the engine's own kernels) -------------------- */
 int  azg_profile_enable(azg_engine *e, int on);
