@@ -174,6 +174,17 @@ def check(rc):
     return rc
 
 
+def stream():
+    """the current torch stream, as the `stream` argument of every launch (SYMBOLS declares it c_void_p: a plain int is accepted)"""
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def ptr(t):
+    """a tensor's device address as a c_void_p argument; None (a null pointer) for None"""
+    return None if t is None else t.data_ptr()
+
+
 def game_info(game):
     gi = GameInfo()
     check(lib().azg_game_info_get(game, C.byref(gi)))

@@ -30,6 +30,60 @@ static thread_local EvPair *g_kev = nullptr;
     if (g_kev) { hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, g_kev->a, g_kev->b, 0, __VA_ARGS__); g_kev = nullptr; } \
     else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); } while (0)
 
+// One profile record (every engine has one: azg_profile_*; the network launches share one: azg_profile_net_*): per launch family the
+// event pairs still in flight, the milliseconds and launches counted so far, and the idle pairs
+struct Prof {
+    bool on = false;
+    std::vector<EvPair> ev[3], pool;
+    double ms[3] = {0, 0, 0};
+    int64_t n[3] = {0, 0, 0};
+    EvPair take() {
+        EvPair p{};
+        if (!pool.empty()) { p = pool.back(); pool.pop_back(); }
+        else { (void)hipEventCreate(&p.a); (void)hipEventCreate(&p.b); }
+        return p;
+    }
+    void done(int fam, const EvPair &p) { ev[fam].push_back(p); n[fam]++; }
+    void drain() {
+        for (int f = 0; f < 3; f++) {
+            for (auto &p : ev[f]) {
+                (void)hipEventSynchronize(p.b);
+                float t = 0; (void)hipEventElapsedTime(&t, p.a, p.b);
+                ms[f] += t;
+                pool.push_back(p);
+            }
+            ev[f].clear();
+        }
+    }
+    void enable(bool v) { drain(); on = v; if (v) for (int f = 0; f < 3; f++) { ms[f] = 0; n[f] = 0; } }
+    void read(double *ms3, int64_t *launches3) { drain(); for (int f = 0; f < 3; f++) { ms3[f] = ms[f]; launches3[f] = n[f]; } }
+};
+
+// One timed region of family `fam`, open for as long as the object lives.  one_kernel: the region is ONE AZG_LAUNCH, timed through g_kev;
+// otherwise a sequence of launches between two event records.  However the region is left, g_kev is clear afterwards and the pair goes
+// back: to the family's list if a launch took it (AZG_LAUNCH resets g_kev), to the pool -- nothing counted -- if none did.
+class ProfScope {
+    Prof *prof = nullptr; std::mutex *mu; hipStream_t s; int fam; EvPair p{};
+    std::unique_lock<std::mutex> lock() const { return mu ? std::unique_lock<std::mutex>(*mu) : std::unique_lock<std::mutex>(); }
+public:
+    ProfScope(Prof &pr, std::mutex *mu_, hipStream_t s_, int fam_, bool one_kernel = true, bool enabled = true) : mu(mu_), s(s_), fam(fam_) {
+        if (!enabled) return;
+        { auto lk = lock(); if (!pr.on) return; p = pr.take(); }
+        prof = &pr; p.ext = one_kernel;
+        if (p.ext) g_kev = &p; else (void)hipEventRecord(p.a, s);
+    }
+    ~ProfScope() {
+        if (!prof) return;
+        const bool launched = !p.ext || g_kev != &p;
+        if (!p.ext) (void)hipEventRecord(p.b, s);
+        g_kev = nullptr;
+        auto lk = lock();
+        if (launched) prof->done(fam, p); else prof->pool.push_back(p);
+    }
+    ProfScope(const ProfScope &) = delete;
+    ProfScope &operator=(const ProfScope &) = delete;
+};
+
 struct azg_engine {
     azg_config cfg;
     azg_game_info gi;
@@ -38,11 +92,7 @@ struct azg_engine {
     int32_t *d_p2i = nullptr, *d_ok = nullptr;
     int16_t *d_perm = nullptr;                                 // azg_set_shuffle_tape / azg_set_random_tape
     double *d_utape = nullptr; int32_t *d_noff = nullptr; float *d_npool = nullptr;
-    bool profile = false;
-    std::vector<EvPair> ev[3];
-    double ms[3] = {0, 0, 0};
-    int64_t launches[3] = {0, 0, 0};
-    std::vector<EvPair> pool;
+    Prof prof;
 };
 
 // the game table and everything else per game below: expanded from the one list of rule structs (AZG_GAMES, azg_games.h)
@@ -107,32 +157,6 @@ template <typename T> static int dalloc(azg_engine *e, T **p, size_t count) {
     if ((obs_dtype) == 0) { using OBS = float; constexpr bool NHWC8 = false; OBS *const o = (OBS *)(obs); CALL; } \
     else if ((obs_dtype) == 1) { using OBS = _Float16; constexpr bool NHWC8 = false; OBS *const o = (OBS *)(obs); CALL; } \
     else { using OBS = _Float16; constexpr bool NHWC8 = true; OBS *const o = (OBS *)(obs); CALL; }
-
-static void prof_begin(azg_engine *e, hipStream_t s, int fam, EvPair &p) {
-    if (!e->profile) return;
-    if (!e->pool.empty()) { p = e->pool.back(); e->pool.pop_back(); }
-    else { (void)hipEventCreate(&p.a); (void)hipEventCreate(&p.b); }
-    p.ext = fam != 2;                                          // select / backup: one kernel each; advance: a sequence of launches
-    if (p.ext) g_kev = &p; else (void)hipEventRecord(p.a, s);
-}
-static void prof_end(azg_engine *e, hipStream_t s, int fam, EvPair &p) {
-    if (!e->profile) return;
-    if (!p.ext) (void)hipEventRecord(p.b, s);
-    g_kev = nullptr;
-    e->ev[fam].push_back(p);
-    e->launches[fam]++;
-}
-static void prof_drain(azg_engine *e) {
-    for (int f = 0; f < 3; f++) {
-        for (auto &p : e->ev[f]) {
-            (void)hipEventSynchronize(p.b);
-            float t = 0; (void)hipEventElapsedTime(&t, p.a, p.b);
-            e->ms[f] += t;
-            e->pool.push_back(p);
-        }
-        e->ev[f].clear();
-    }
-}
 
 extern "C" int azg_engine_create(const azg_config *cfg, azg_engine **out) {
     if (!cfg || !out) return fail(AZG_E_INVALID_ARG, "null argument");
@@ -205,8 +229,8 @@ extern "C" int azg_engine_create(const azg_config *cfg, azg_engine **out) {
 extern "C" int azg_engine_destroy(azg_engine *e) {
     if (!e) return AZG_OK;
     (void)hipDeviceSynchronize();
-    prof_drain(e);
-    for (auto &p : e->pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
+    e->prof.drain();
+    for (auto &p : e->prof.pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (void *p : e->allocs) (void)hipFree(p);
     if (e->d_perm) (void)hipFree(e->d_perm);
     if (e->d_utape) (void)hipFree(e->d_utape);
@@ -275,9 +299,8 @@ extern "C" int azg_select(azg_engine *e, void *stream, void *obs, int obs_dtype,
     if (!e) return fail(AZG_E_INVALID_ARG, "null engine");
     if (obs_dtype < 0 || obs_dtype > 2) return fail(AZG_E_INVALID_ARG, "obs_dtype must be 0 (f32), 1 (f16) or 2 (f16 NHWC8)");
     hipStream_t s = (hipStream_t)stream;
-    EvPair p; prof_begin(e, s, 0, p);
+    ProfScope timed(e->prof, nullptr, s, 0);
     OBS_SWITCH(obs_dtype, obs, GAME_SWITCH(e, AZG_LAUNCH((k_select<G, OBS, NHWC8>), dim3(e->v.B), dim3(64), 0, s, e->v, o, row_of_slot)));
-    prof_end(e, s, 0, p);
     HIPCHK(hipGetLastError());
     return AZG_OK;
 }
@@ -306,9 +329,8 @@ extern "C" int azg_backup(azg_engine *e, void *stream, const float *policy, cons
     hipStream_t s = (hipStream_t)stream;
     View v = e->v;
     if (flags >= 0) { v.add_noise = (flags & AZG_FLAG_NOISE) ? 1 : 0; v.add_temp = (flags & AZG_FLAG_TEMP) ? 1 : 0; }
-    EvPair p; prof_begin(e, s, 1, p);
+    ProfScope timed(e->prof, nullptr, s, 1);
     GAME_SWITCH(e, AZG_LAUNCH((k_backup<G>), dim3(e->v.B), dim3(64), 0, s, v, policy, value, row_of_slot));
-    prof_end(e, s, 1, p);
     HIPCHK(hipGetLastError());
     return AZG_OK;
 }
@@ -334,10 +356,9 @@ extern "C" int azg_backup_select(azg_engine *e, void *stream, const float *polic
     hipStream_t s = (hipStream_t)stream;
     View v = e->v;
     if (flags >= 0) { v.add_noise = (flags & AZG_FLAG_NOISE) ? 1 : 0; v.add_temp = (flags & AZG_FLAG_TEMP) ? 1 : 0; }
-    EvPair p; prof_begin(e, s, 1, p);
+    ProfScope timed(e->prof, nullptr, s, 1);
     const int A = e->gi.action_size;
     OBS_SWITCH(obs_dtype, obs, GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, OBS, NHWC8, IN_PROBS>), dim3(v.B), dim3(128), 0, s, v, policy, value, A, o, row_of_slot, 1, HeadRows{})));
-    prof_end(e, s, 1, p);
     HIPCHK(hipGetLastError());
     return AZG_OK;
 }
@@ -351,10 +372,9 @@ extern "C" int azg_backup_select_logits(azg_engine *e, void *stream, const float
     hipStream_t s = (hipStream_t)stream;
     View v = e->v;
     if (flags >= 0) { v.add_noise = (flags & AZG_FLAG_NOISE) ? 1 : 0; v.add_temp = (flags & AZG_FLAG_TEMP) ? 1 : 0; }
-    EvPair p; prof_begin(e, s, 1, p);
+    ProfScope timed(e->prof, nullptr, s, 1);
     const float *nov = nullptr;
     OBS_SWITCH(obs_dtype, obs, GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, OBS, NHWC8, IN_LOGITS>), dim3(v.B), dim3(128), 0, s, v, logits, nov, logits_stride, o, row_of_slot, do_select, HeadRows{})));
-    prof_end(e, s, 1, p);
     HIPCHK(hipGetLastError());
     return AZG_OK;
 }
@@ -371,10 +391,9 @@ extern "C" int azg_backup_select_features(azg_engine *e, void *stream, const voi
     int want = 0;
     SPARSE_GAME_SWITCH(e, want = head_fk<G>());
     if (feat_k != want) return fail(AZG_E_INVALID_ARG, "feat_k must be cells x 16 rounded up to a multiple of 32 for this game");
-    EvPair p; prof_begin(e, s, 1, p);
+    ProfScope timed(e->prof, nullptr, s, 1);
     const float *nov = nullptr, *f = (const float *)feat;
     OBS_SWITCH(obs_dtype, obs, SPARSE_GAME_SWITCH(e, AZG_LAUNCH((k_backup_select2<G, OBS, NHWC8, IN_FEATURES>), dim3(v.B), dim3(128), 0, s, v, f, nov, 0, o, row_of_slot, do_select, hd)));
-    prof_end(e, s, 1, p);
     HIPCHK(hipGetLastError());
     return AZG_OK;
 }
@@ -397,7 +416,7 @@ extern "C" int azg_leaf_heads_sparse_f16(azg_engine *e, void *stream, const void
 // playMoves and what follows it, for azg_advance (actions == nullptr: k_play<G>, every move from the trees) and azg_advance_actions
 // (k_play<G, true>: the slots with an action >= 0 play it): one launch sequence, so that the two cannot drift apart
 static int advance_launches(azg_engine *e, hipStream_t s, int record_history, const int32_t *actions) {
-    EvPair p; prof_begin(e, s, 2, p);
+    ProfScope timed(e->prof, nullptr, s, 2, false);
     GAME_SWITCH(e, {
         if (actions) hipLaunchKernelGGL((k_play<G, true>), dim3(e->v.B), dim3(64), 0, s, e->v, record_history, actions);
         else hipLaunchKernelGGL((k_play<G>), dim3(e->v.B), dim3(64), 0, s, e->v, record_history, (const int32_t *)nullptr);
@@ -406,7 +425,6 @@ static int advance_launches(azg_engine *e, hipStream_t s, int record_history, co
         hipLaunchKernelGGL((k_emit<G>), dim3(e->v.B), dim3(64), 0, s, e->v);
         hipLaunchKernelGGL((k_compact<G>), dim3(e->v.B * e->v.T), dim3(64), 0, s, e->v, 0, 0);
     });
-    prof_end(e, s, 2, p);
     HIPCHK(hipGetLastError());
     return AZG_OK;
 }
@@ -821,6 +839,69 @@ extern "C" int azg_states_dev(azg_engine *e, const azg_state **states) {
     return AZG_OK;
 }
 
+#ifdef AZG_TOWER_TIMING
+// measurement builds only: the stamp buffer of ONE k_tower2 instantiation and its dump to stderr -- a persistent wide-head launch after
+// every launch (phase means over the workgroups, the helper wavefront, the layers of workgroup 0), any other tile after its 8th launch
+// (the layers of workgroup 0, every workgroup's phases)
+template <int H, int W, int BOARDS, int C, int PSPLIT, class SEARCH, int KSPLIT>
+struct TowerTiming {
+    static int stamps(unsigned long long **out) {
+        if (!dbg()) { HIPCHK(hipMalloc((void **)&dbg(), (2048 + 4096 * 8) * 8)); HIPCHK(hipMemset(dbg(), 0, (2048 + 4096 * 8) * 8)); }
+        *out = dbg();
+        return AZG_OK;
+    }
+    static int dump(hipStream_t s, const TowerParams &P, const SEARCH &sa, int grid) {
+        constexpr bool IS_SEARCH = !__is_same(SEARCH, NoSearch);
+        unsigned long long *const dbg = TowerTiming::dbg();
+        static int calls = 0;
+        (void)sa;
+        if constexpr (IS_SEARCH) if constexpr (SEARCH::WIDE) {
+            static unsigned long long w[512 * 4];
+            HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipMemcpy(w, dbg + 2048 + 4096 * 4, sizeof(unsigned long long) * 4 * (grid < 512 ? grid : 512), hipMemcpyDeviceToHost));
+            double ph[4] = {0, 0, 0, 0}; const int nb = grid < 512 ? grid : 512;
+            for (int b = 0; b < nb; b++) for (int i = 0; i < 4; i++) ph[i] += (double)w[b * 4 + i];
+            const double n = (double)nb * (sa.sims > 8 ? sa.sims - 8 : 1);
+            fprintf(stderr, "wide search, cycles per simulation (mean over %d workgroups): tree %.0f tower %.0f headconv %.0f heads %.0f\n", nb, ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n);
+            HIPCHK(hipMemset(dbg + 2048 + 4096 * 4, 0, sizeof(unsigned long long) * 4 * 512));
+            static unsigned long long hw_[512 * 8];
+            HIPCHK(hipMemcpy(hw_, dbg + 2048 + 4096 * 5, sizeof(unsigned long long) * 8 * nb, hipMemcpyDeviceToHost));
+            double hp[5] = {0, 0, 0, 0, 0}, hn = 0;
+            for (int b = 0; b < nb; b++) { for (int i = 0; i < 5; i++) hp[i] += (double)hw_[b * 8 + i]; hn += (double)hw_[b * 8 + 5]; }
+            if (hn > 0) fprintf(stderr, "  helper wavefront (cycles per simulation with a policy backup): header %.0f masks %.0f logits %.0f softmax %.0f priors %.0f\n",
+                                hp[0] / hn, hp[1] / hn, hp[2] / hn, hp[3] / hn, hp[4] / hn);
+            HIPCHK(hipMemset(dbg + 2048 + 4096 * 5, 0, sizeof(unsigned long long) * 8 * 512));
+            {                                                       // the layers of workgroup 0's last simulation (all wavefronts of the workgroup)
+                unsigned long long h[64 * 4 * 5];
+                HIPCHK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
+                for (int l = 0; l <= 2 * P.nblocks; l++) for (int w = 0; w < C / 32 * PSPLIT * KSPLIT && w < 4; w++) {
+                    unsigned long long *t = h + (l * 4 + w) * 5;
+                    fprintf(stderr, "  layer %2d wave %d: main %6llu wait %6llu epi %6llu bar %6llu | start %llu\n", l, w, t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[0] - h[0]);
+                }
+            }
+            calls = 100;
+        }
+        if (++calls == 8) {
+            unsigned long long h[64 * 4 * 5];
+            HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
+            for (int l = 0; l <= 2 * P.nblocks; l++) for (int w = 0; w < C / 32; w++) {
+                unsigned long long *t = h + (l * 4 + w) * 5;
+                fprintf(stderr, "layer %2d wave %d: main %6llu wait %6llu epi %6llu bar %6llu | start %llu\n", l, w, t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[0] - h[0]);
+            }
+            static unsigned long long w[4096 * 8];
+            HIPCHK(hipMemcpy(w, dbg + 2048, sizeof(unsigned long long) * 8 * grid, hipMemcpyDeviceToHost));
+            unsigned long long x2[1024];
+            HIPCHK(hipMemcpy(x2, dbg + 1024, sizeof(x2), hipMemcpyDeviceToHost));
+            for (int b = 0; b < grid && b < 512; b++) fprintf(stderr, "wgx %4d xload+store %llu weights %llu\n", b, x2[b * 2] - w[b * 8], x2[b * 2 + 1] - x2[b * 2]);
+            for (int b = 0; b < grid; b++) fprintf(stderr, "wg %4d xcc %llu hwid %08llx start %llu end %llu | prologue %llu layers %llu headmm %llu softmax %llu tail %llu\n", b, w[b * 8 + 3] & 15, w[b * 8 + 2], w[b * 8], w[b * 8 + 1],
+                                                   w[b * 8 + 4] - w[b * 8], w[b * 8 + 5] - w[b * 8 + 4], w[b * 8 + 6] - w[b * 8 + 5], w[b * 8 + 7] - w[b * 8 + 6], w[b * 8 + 1] - w[b * 8 + 7]);
+        }
+        return AZG_OK;
+    }
+private:
+    static unsigned long long *&dbg() { static unsigned long long *d = nullptr; return d; }
+};
+#endif
+
 // occ (optional): the workgroups of THIS instantiation a CU of this device holds at once (the occupancy query with the launch's own LDS
 // size) -- what the tile choice of the persistent launches is derived from instead of a constant for one chip
 template <int H, int W, int BOARDS, int C, int PSPLIT = 1, class SEARCH = NoSearch, int KSPLIT = 1>
@@ -878,50 +959,11 @@ static int launch_tower(hipStream_t s, const TowerParams &P, SEARCH sa = SEARCH{
         // (search mode: every tile is its own workgroup for the whole launch -- they never synchronise, later ones just start later)
         const int grid = IS_SEARCH || ntiles < per_cu * cus ? ntiles : per_cu * cus;
 #ifdef AZG_TOWER_TIMING
-        static unsigned long long *dbg = nullptr; static int calls = 0;
-        if (!dbg) { HIPCHK(hipMalloc((void **)&dbg, (2048 + 4096 * 8) * 8)); HIPCHK(hipMemset(dbg, 0, (2048 + 4096 * 8) * 8)); }
-        TowerParams Q = P; Q.dbg = dbg;
+        using TT = TowerTiming<H, W, BOARDS, C, PSPLIT, SEARCH, KSPLIT>;
+        TowerParams Q = P;
+        { const int r = TT::stamps(&Q.dbg); if (r != AZG_OK) return r; }
         AZG_LAUNCH((k_tower2<H, W, BOARDS, C, PSPLIT, SEARCH, KSPLIT>), dim3(grid), dim3(C * 2 * PSPLIT * KSPLIT), LDS_BYTES, s, Q, (const int16_t *)d_map[dev], sa);
-        if constexpr (IS_SEARCH) if constexpr (SEARCH::WIDE) {
-            static unsigned long long w[512 * 4];
-            HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipMemcpy(w, dbg + 2048 + 4096 * 4, sizeof(unsigned long long) * 4 * (grid < 512 ? grid : 512), hipMemcpyDeviceToHost));
-            double ph[4] = {0, 0, 0, 0}; const int nb = grid < 512 ? grid : 512;
-            for (int b = 0; b < nb; b++) for (int i = 0; i < 4; i++) ph[i] += (double)w[b * 4 + i];
-            const double n = (double)nb * (sa.sims > 8 ? sa.sims - 8 : 1);
-            fprintf(stderr, "wide search, cycles per simulation (mean over %d workgroups): tree %.0f tower %.0f headconv %.0f heads %.0f\n", nb, ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n);
-            HIPCHK(hipMemset(dbg + 2048 + 4096 * 4, 0, sizeof(unsigned long long) * 4 * 512));
-            static unsigned long long hw_[512 * 8];
-            HIPCHK(hipMemcpy(hw_, dbg + 2048 + 4096 * 5, sizeof(unsigned long long) * 8 * nb, hipMemcpyDeviceToHost));
-            double hp[5] = {0, 0, 0, 0, 0}, hn = 0;
-            for (int b = 0; b < nb; b++) { for (int i = 0; i < 5; i++) hp[i] += (double)hw_[b * 8 + i]; hn += (double)hw_[b * 8 + 5]; }
-            if (hn > 0) fprintf(stderr, "  helper wavefront (cycles per simulation with a policy backup): header %.0f masks %.0f logits %.0f softmax %.0f priors %.0f\n",
-                                hp[0] / hn, hp[1] / hn, hp[2] / hn, hp[3] / hn, hp[4] / hn);
-            HIPCHK(hipMemset(dbg + 2048 + 4096 * 5, 0, sizeof(unsigned long long) * 8 * 512));
-            {                                                       // the layers of workgroup 0's last simulation (all wavefronts of the workgroup)
-                unsigned long long h[64 * 4 * 5];
-                HIPCHK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
-                for (int l = 0; l <= 2 * P.nblocks; l++) for (int w = 0; w < C / 32 * PSPLIT * KSPLIT && w < 4; w++) {
-                    unsigned long long *t = h + (l * 4 + w) * 5;
-                    fprintf(stderr, "  layer %2d wave %d: main %6llu wait %6llu epi %6llu bar %6llu | start %llu\n", l, w, t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[0] - h[0]);
-                }
-            }
-            calls = 100;
-        }
-        if (++calls == 8) {
-            unsigned long long h[64 * 4 * 5];
-            HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
-            for (int l = 0; l <= 2 * P.nblocks; l++) for (int w = 0; w < C / 32; w++) {
-                unsigned long long *t = h + (l * 4 + w) * 5;
-                fprintf(stderr, "layer %2d wave %d: main %6llu wait %6llu epi %6llu bar %6llu | start %llu\n", l, w, t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[0] - h[0]);
-            }
-            static unsigned long long w[4096 * 8];
-            HIPCHK(hipMemcpy(w, dbg + 2048, sizeof(unsigned long long) * 8 * grid, hipMemcpyDeviceToHost));
-            unsigned long long x2[1024];
-            HIPCHK(hipMemcpy(x2, dbg + 1024, sizeof(x2), hipMemcpyDeviceToHost));
-            for (int b = 0; b < grid && b < 512; b++) fprintf(stderr, "wgx %4d xload+store %llu weights %llu\n", b, x2[b * 2] - w[b * 8], x2[b * 2 + 1] - x2[b * 2]);
-            for (int b = 0; b < grid; b++) fprintf(stderr, "wg %4d xcc %llu hwid %08llx start %llu end %llu | prologue %llu layers %llu headmm %llu softmax %llu tail %llu\n", b, w[b * 8 + 3] & 15, w[b * 8 + 2], w[b * 8], w[b * 8 + 1],
-                                                   w[b * 8 + 4] - w[b * 8], w[b * 8 + 5] - w[b * 8 + 4], w[b * 8 + 6] - w[b * 8 + 5], w[b * 8 + 7] - w[b * 8 + 6], w[b * 8 + 1] - w[b * 8 + 7]);
-        }
+        { const int r = TT::dump(s, P, sa, grid); if (r != AZG_OK) return r; }
 #else
         AZG_LAUNCH((k_tower2<H, W, BOARDS, C, PSPLIT, SEARCH, KSPLIT>), dim3(grid), dim3(C * 2 * PSPLIT * KSPLIT), LDS_BYTES, s, P, (const int16_t *)d_map[dev], sa);
 #endif
@@ -930,49 +972,20 @@ static int launch_tower(hipStream_t s, const TowerParams &P, SEARCH sa = SEARCH{
     return AZG_OK;
 }
 
-// ---- timing hooks for the network launches (no engine handle there: process-wide, same event scheme as azg_profile_*) ----------
-struct NetProf {
-    std::mutex mu; bool on = false;
-    std::vector<EvPair> ev[3], pool;
-    double ms[3] = {0, 0, 0}; int64_t n[3] = {0, 0, 0};
+// ---- timing hooks for the network launches (no engine handle there: one record for the process, behind a mutex) -----------------
+static struct { std::mutex mu; Prof prof; } g_netprof;
+struct NetProfScope : ProfScope {
+    NetProfScope(hipStream_t s, int fam, bool enabled = true) : ProfScope(g_netprof.prof, &g_netprof.mu, s, fam, true, enabled) {}
 };
-static NetProf g_netprof;
-static bool netprof_begin(hipStream_t s, EvPair &p) {
-    std::lock_guard<std::mutex> lk(g_netprof.mu);
-    if (!g_netprof.on) return false;
-    if (!g_netprof.pool.empty()) { p = g_netprof.pool.back(); g_netprof.pool.pop_back(); }
-    else { (void)hipEventCreate(&p.a); (void)hipEventCreate(&p.b); }
-    p.ext = true; g_kev = &p; (void)s;
-    return true;
-}
-static void netprof_end(hipStream_t s, int fam, bool on, EvPair &p) {
-    if (!on) return;
-    g_kev = nullptr; (void)s;
-    std::lock_guard<std::mutex> lk(g_netprof.mu);
-    g_netprof.ev[fam].push_back(p); g_netprof.n[fam]++;
-}
-static void netprof_drain() {
-    for (int f = 0; f < 3; f++) {
-        for (auto &p : g_netprof.ev[f]) {
-            (void)hipEventSynchronize(p.b);
-            float t = 0; (void)hipEventElapsedTime(&t, p.a, p.b);
-            g_netprof.ms[f] += t; g_netprof.pool.push_back(p);
-        }
-        g_netprof.ev[f].clear();
-    }
-}
 extern "C" int azg_profile_net_enable(int on) {
     std::lock_guard<std::mutex> lk(g_netprof.mu);
-    netprof_drain();
-    g_netprof.on = on != 0;
-    if (on) for (int f = 0; f < 3; f++) { g_netprof.ms[f] = 0; g_netprof.n[f] = 0; }
+    g_netprof.prof.enable(on != 0);
     return AZG_OK;
 }
 extern "C" int azg_profile_net_read(double *ms3, int64_t *launches3) {
     if (!ms3 || !launches3) return fail(AZG_E_INVALID_ARG, "null argument");
     std::lock_guard<std::mutex> lk(g_netprof.mu);
-    netprof_drain();
-    for (int f = 0; f < 3; f++) { ms3[f] = g_netprof.ms[f]; launches3[f] = g_netprof.n[f]; }
+    g_netprof.prof.read(ms3, launches3);
     return AZG_OK;
 }
 
@@ -1022,6 +1035,65 @@ static void set_fact_heads(TowerParams &P, const void *head1_w, const float *hea
     P.head1_w = head1_w; P.head1_b = head1_b; P.feat = feat; P.feat_k = feat_k;
 }
 
+// ---- argument checks and fills the launches below share (`if (int r = ...) return r;`: AZG_OK is 0) ------------------------------------
+// a tower with residual blocks needs their affines
+static int check_affine(int nblocks, const void *pre_scale, const void *pre_shift) {
+    return nblocks > 0 && (!pre_scale || !pre_shift) ? fail(AZG_E_INVALID_ARG, "pre_scale/pre_shift required") : AZG_OK;
+}
+// the head features of the persistent wide-head launches: 16 per cell
+static int check_search_feat_k(const azg_engine *e, int feat_k) {
+    const int hw = e->gi.obs_h * e->gi.obs_w;
+    return feat_k != (hw * 16 + 31) / 32 * 32 ? fail(AZG_E_INVALID_ARG, "feat_k must be H*W*16 rounded up to 32") : AZG_OK;
+}
+// player -> model of an arena launch, from the host's player_to_index (null: the launch seats by slot, seat_of_slot)
+static int seat_map(const azg_engine *e, const int32_t *p2i_host, int nmodels, SeatMap &seat) {
+    if (p2i_host) for (int i = 0; i < e->gi.num_players && i < 8; i++) {
+        if (p2i_host[i] < 0 || p2i_host[i] >= nmodels) return fail(AZG_E_INVALID_ARG, "player_to_index entry out of range");
+        seat.v[i] = p2i_host[i];
+    }
+    return AZG_OK;
+}
+// TowerParams of a fused-heads launch of `nmodels` models (model 0: the tower's own fields, model m > 0: alt[m - 1]); every model brings
+// all its parameters
+static int fused_models_params(TowerParams &P, const void *x, int boards, float *policy, float *value, int A, int NV, int nmodels, const void *const *w,
+                               const float *const *bias, const float *const *pre_scale, const float *const *pre_shift, int nblocks,
+                               const void *const *head_w, const float *const *head_b) {
+    for (int m = 0; m < nmodels; m++)
+        if (!w[m] || !bias[m] || !head_w[m] || !head_b[m] || (nblocks > 0 && (!pre_scale || !pre_shift || !pre_scale[m] || !pre_shift[m])))
+            return fail(AZG_E_INVALID_ARG, "null model parameter");
+    const auto model = [&](int m) {
+        return TowerParams::Model{w[m], bias[m], nblocks ? pre_scale[m] : nullptr, nblocks ? pre_shift[m] : nullptr, head_w[m], head_b[m]};
+    };
+    const TowerParams::Model m0 = model(0);
+    P = tower_params(x, m0.w, m0.bias, m0.pre_scale, m0.pre_shift, boards, nblocks);
+    set_fused_heads(P, m0.head_w, m0.head_b, policy, value, A, NV); P.nmodels = nmodels;
+    for (int m = 1; m < nmodels; m++) P.alt[m - 1] = model(m);
+    return AZG_OK;
+}
+
+// the end of every stand-alone tower entry point: the launch's tile for this device, timed as the tower family
+static int run_tower(void *stream, int game, int channels, const TowerParams &P) {
+    NetProfScope timed((hipStream_t)stream, 0);
+    return dispatch_tower((hipStream_t)stream, game, channels, P);
+}
+
+// The fused search launches (azg_search_f16, azg_search_arena_f16) run on the rows of AZG_TOWER_TILES that is_fused_search_tile names
+// (azg_tiles.h): SA's kernel on the row of bt games per workgroup.  The arena launch is built for one game per workgroup only.
+template <class SA, class G, int C, int BT, int PS, int KS> constexpr bool fused_search_row = is_fused_search_tile<G, C, PS, KS> && (BT == 1 || !SA::ARENA);
+template <class G, int C, int BT, int PS, int KS, class SA>
+static int fused_search_tile_launch(hipStream_t s, const TowerParams &P, const SA &sa, bool init) {
+    if constexpr (fused_search_row<SA, G, C, BT, PS, KS>) return launch_tower<G::H, G::W, BT, C, PS, SA, KS>(s, P, sa, init);
+    else return AZG_E_UNSUPPORTED;
+}
+template <class SA>
+static int fused_search_launch(hipStream_t s, const TowerParams &P, const SA &sa, int bt, bool init) {
+#define AZG_ROW(G, C, BT, PS, KS, LIMIT) \
+    if (fused_search_row<SA, G, C, BT, PS, KS> && bt == BT) return fused_search_tile_launch<G, C, BT, PS, KS>(s, P, sa, init);
+    AZG_TOWER_TILES(AZG_ROW)
+#undef AZG_ROW
+    return fail(AZG_E_INTERNAL, "the fused search kernel has no tile of this many games per workgroup");
+}
+
 // [boards, C, H*W] f32 planes (what GameState.observation / the reference's batch tensors hold) -> the tower's input rows [boards * H*W][8] fp16
 __global__ __launch_bounds__(256) void k_obs_to_nhwc8(const float *src, half8 *dst, int n, int C, int HW) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -1042,26 +1114,20 @@ extern "C" int azg_obs_to_nhwc8_f16(void *stream, const float *obs, int boards, 
 extern "C" int azg_resnet_tower_f16(void *stream, int game, const void *x, const void *w, const float *bias, const float *pre_scale,
                                     const float *pre_shift, void *y, int boards, int nblocks, int channels) {
     if (!x || !w || !bias || !y || boards <= 0 || nblocks < 0) return fail(AZG_E_INVALID_ARG, "null argument");
-    if (nblocks > 0 && (!pre_scale || !pre_shift)) return fail(AZG_E_INVALID_ARG, "pre_scale/pre_shift required");
+    if (int r = check_affine(nblocks, pre_scale, pre_shift)) return r;
     TowerParams P = tower_params(x, w, bias, pre_scale, pre_shift, boards, nblocks); P.y = y;
-    EvPair ep; const bool prof = netprof_begin((hipStream_t)stream, ep);
-    const int r = dispatch_tower((hipStream_t)stream, game, channels, P);
-    netprof_end((hipStream_t)stream, 0, prof, ep);
-    return r;
+    return run_tower(stream, game, channels, P);
 }
 
 extern "C" int azg_resnet_tower_features_f16(void *stream, int game, const void *x, const void *w, const float *bias, const float *pre_scale,
                                              const float *pre_shift, int boards, int nblocks, int channels, const void *head1_w, const float *head1_b,
                                              void *feat, int feat_k) {
     if (!x || !w || !bias || !head1_w || !head1_b || !feat || boards <= 0 || nblocks < 0) return fail(AZG_E_INVALID_ARG, "null argument");
-    if (nblocks > 0 && (!pre_scale || !pre_shift)) return fail(AZG_E_INVALID_ARG, "pre_scale/pre_shift required");
+    if (int r = check_affine(nblocks, pre_scale, pre_shift)) return r;
     if (feat_k <= 0 || (feat_k & 31)) return fail(AZG_E_INVALID_ARG, "feat_k must be a positive multiple of 32");
     TowerParams P = tower_params(x, w, bias, pre_scale, pre_shift, boards, nblocks);
     set_fact_heads(P, head1_w, head1_b, feat, feat_k);
-    EvPair ep; const bool prof = netprof_begin((hipStream_t)stream, ep);
-    const int r = dispatch_tower((hipStream_t)stream, game, channels, P);
-    netprof_end((hipStream_t)stream, 0, prof, ep);
-    return r;
+    return run_tower(stream, game, channels, P);
 }
 
 extern "C" int azg_resnet_policy_value_f16(void *stream, int game, const void *x, const void *w, const float *bias, const float *pre_scale,
@@ -1069,13 +1135,10 @@ extern "C" int azg_resnet_policy_value_f16(void *stream, int game, const void *x
                                            int A, int NV, float *policy, float *value) {
     if (!x || !w || !bias || !head_w || !head_b || !policy || !value || boards <= 0 || nblocks < 0) return fail(AZG_E_INVALID_ARG, "null argument");
     if (A <= 0 || NV <= 0 || A + NV > 16) return fail(AZG_E_UNSUPPORTED, "fused heads need A + NV <= 16");
-    if (nblocks > 0 && (!pre_scale || !pre_shift)) return fail(AZG_E_INVALID_ARG, "pre_scale/pre_shift required");
+    if (int r = check_affine(nblocks, pre_scale, pre_shift)) return r;
     TowerParams P = tower_params(x, w, bias, pre_scale, pre_shift, boards, nblocks);
     set_fused_heads(P, head_w, head_b, policy, value, A, NV);
-    EvPair ep; const bool prof = netprof_begin((hipStream_t)stream, ep);
-    const int r = dispatch_tower((hipStream_t)stream, game, 128, P);
-    netprof_end((hipStream_t)stream, 0, prof, ep);
-    return r;
+    return run_tower(stream, game, 128, P);
 }
 
 extern "C" int azg_resnet_policy_value_multi_f16(void *stream, int game, const void *x, int nmodels, const void *const *w, const float *const *bias,
@@ -1086,43 +1149,29 @@ extern "C" int azg_resnet_policy_value_multi_f16(void *stream, int game, const v
         return fail(AZG_E_INVALID_ARG, "null or out-of-range argument");
     if (nmodels < 1 || nmodels > 4) return fail(AZG_E_UNSUPPORTED, "1 to 4 models per launch");
     if (A <= 0 || NV <= 0 || A + NV > 16) return fail(AZG_E_UNSUPPORTED, "fused heads need A + NV <= 16");
-    if (nblocks > 0 && (!pre_scale || !pre_shift)) return fail(AZG_E_INVALID_ARG, "pre_scale/pre_shift required");
-    for (int m = 0; m < nmodels; m++)
-        if (!w[m] || !bias[m] || !head_w[m] || !head_b[m] || (nblocks > 0 && (!pre_scale[m] || !pre_shift[m]))) return fail(AZG_E_INVALID_ARG, "null model parameter");
+    if (int r = check_affine(nblocks, pre_scale, pre_shift)) return r;
     // the grid is sized for max_boards rows plus one partial tile per extra model
-    TowerParams P = tower_params(x, w[0], bias[0], nblocks ? pre_scale[0] : nullptr, nblocks ? pre_shift[0] : nullptr, max_boards, nblocks);
-    set_fused_heads(P, head_w[0], head_b[0], policy, value, A, NV); P.rows_per_model = rows_per_model; P.nmodels = nmodels;
-    for (int m = 1; m < nmodels; m++)
-        P.alt[m - 1] = TowerParams::Model{w[m], bias[m], nblocks ? pre_scale[m] : nullptr, nblocks ? pre_shift[m] : nullptr, head_w[m], head_b[m]};
-    EvPair ep; const bool prof = netprof_begin((hipStream_t)stream, ep);
-    const int r = dispatch_tower((hipStream_t)stream, game, 128, P);
-    netprof_end((hipStream_t)stream, 0, prof, ep);
-    return r;
+    TowerParams P;
+    if (int r = fused_models_params(P, x, max_boards, policy, value, A, NV, nmodels, w, bias, pre_scale, pre_shift, nblocks, head_w, head_b)) return r;
+    P.rows_per_model = rows_per_model;
+    return run_tower(stream, game, 128, P);
 }
 
 extern "C" int azg_search_f16(azg_engine *e, void *stream, const void *w, const float *bias, const float *pre_scale, const float *pre_shift,
                               int nblocks, const void *head_w, const float *head_b, int sims) {
     if (!e || !w || !bias || !head_w || !head_b || nblocks < 0 || sims < 0) return fail(AZG_E_INVALID_ARG, "null or out-of-range argument");
-    if (nblocks > 0 && (!pre_scale || !pre_shift)) return fail(AZG_E_INVALID_ARG, "pre_scale/pre_shift required");
+    if (int r = check_affine(nblocks, pre_scale, pre_shift)) return r;
     if (e->cfg.game != AZG_GAME_CONNECT4 || e->v.arena)
         return fail(AZG_E_UNSUPPORTED, "the fused search kernel is built for connect4 self-play with a 128-channel tower (use azg_select / network / azg_backup)");
     const int A = e->gi.action_size, NV = e->gi.num_players + 1;
     TowerParams P = tower_params(nullptr, w, bias, pre_scale, pre_shift, e->v.B, nblocks);
     set_fused_heads(P, head_w, head_b, nullptr, nullptr, A, NV);
-    SearchArgs<C4> sa{e->v, sims};
-    EvPair ep; const bool prof = sims > 0 && netprof_begin((hipStream_t)stream, ep);
     // games per workgroup: the stand-alone tower's tile for as many boards (tower_tile_pick).  Small engines -- the single-tree MCTS class, config 1's 32 games --
     // take one game per workgroup (a lone 4-board tile runs at the tower's latency for four boards: 170 us per simulation against ~60)
-    int r, cus = 1;
-    r = device_cus(&cus); if (r != AZG_OK) { g_kev = nullptr; return r; }
-    switch (tower_tile_pick(AZG_GAME_CONNECT4, 128, e->v.B, cus).bt) {                                    // sims == 0: set up only
-    case 1: r = launch_tower<C4::H, C4::W, 1, 128, 1, SearchArgs<C4>>((hipStream_t)stream, P, sa, sims == 0); break;
-    case 2: r = launch_tower<C4::H, C4::W, 2, 128, 1, SearchArgs<C4>>((hipStream_t)stream, P, sa, sims == 0); break;
-    case 4: r = launch_tower<C4::H, C4::W, 4, 128, 1, SearchArgs<C4>>((hipStream_t)stream, P, sa, sims == 0); break;
-    default: r = fail(AZG_E_INTERNAL, "the fused search kernel has no tile of this many games per workgroup");
-    }
-    netprof_end((hipStream_t)stream, 2, prof, ep);
-    return r;
+    int cus = 1;
+    if (int r = device_cus(&cus)) return r;
+    NetProfScope timed((hipStream_t)stream, 2, sims > 0);
+    return fused_search_launch((hipStream_t)stream, P, SearchArgs<C4>{e->v, sims}, tower_tile_pick(AZG_GAME_CONNECT4, 128, e->v.B, cus).bt, sims == 0);   // sims == 0: set up only
 }
 
 extern "C" int azg_search_arena_f16(azg_engine *e, void *stream, int nmodels, const void *const *w, const float *const *bias, const float *const *pre_scale,
@@ -1132,22 +1181,13 @@ extern "C" int azg_search_arena_f16(azg_engine *e, void *stream, int nmodels, co
     if (e->cfg.game != AZG_GAME_CONNECT4 || !e->v.arena)
         return fail(AZG_E_UNSUPPORTED, "the persistent arena launch is built for connect4 arena engines with 128-channel towers (use azg_select / network / azg_backup)");
     if (nmodels < 1 || nmodels > 4 || nmodels < e->gi.num_players) return fail(AZG_E_UNSUPPORTED, "one model per player, at most 4");
-    for (int m = 0; m < nmodels; m++)
-        if (!w[m] || !bias[m] || !head_w[m] || !head_b[m] || (nblocks > 0 && (!pre_scale || !pre_shift || !pre_scale[m] || !pre_shift[m]))) return fail(AZG_E_INVALID_ARG, "null model parameter");
-    const int A = e->gi.action_size, NV = e->gi.num_players + 1;
-    TowerParams P = tower_params(nullptr, w[0], bias[0], nblocks ? pre_scale[0] : nullptr, nblocks ? pre_shift[0] : nullptr, e->v.B, nblocks);
-    set_fused_heads(P, head_w[0], head_b[0], nullptr, nullptr, A, NV); P.nmodels = nmodels;
-    for (int m = 1; m < nmodels; m++)
-        P.alt[m - 1] = TowerParams::Model{w[m], bias[m], nblocks ? pre_scale[m] : nullptr, nblocks ? pre_shift[m] : nullptr, head_w[m], head_b[m]};
+    TowerParams P;
+    if (int r = fused_models_params(P, nullptr, e->v.B, nullptr, nullptr, e->gi.action_size, e->gi.num_players + 1, nmodels, w, bias, pre_scale, pre_shift,
+                                    nblocks, head_w, head_b)) return r;
     SearchArena<C4> sa{e->v, sims, SeatMap{}, seat_of_slot};
-    if (p2i_host) for (int i = 0; i < e->gi.num_players && i < 8; i++) {
-        if (p2i_host[i] < 0 || p2i_host[i] >= nmodels) return fail(AZG_E_INVALID_ARG, "player_to_index entry out of range");
-        sa.seat.v[i] = p2i_host[i];
-    }
-    EvPair ep; const bool prof = sims > 0 && netprof_begin((hipStream_t)stream, ep);
-    const int r = launch_tower<C4::H, C4::W, 1, 128, 1, SearchArena<C4>>((hipStream_t)stream, P, sa, sims == 0);   // sims == 0: set up only
-    netprof_end((hipStream_t)stream, 2, prof, ep);
-    return r;
+    if (int r = seat_map(e, p2i_host, nmodels, sa.seat)) return r;
+    NetProfScope timed((hipStream_t)stream, 2, sims > 0);
+    return fused_search_launch((hipStream_t)stream, P, sa, 1, sims == 0);   // sims == 0: set up only
 }
 
 // ---- the persistent wide-head search launch: tiles, the device-derived tile model, the set-up autotune ----------------------------------
@@ -1294,19 +1334,15 @@ static int wide_tile_pick(azg_engine *e, hipStream_t s, const TowerParams &P, in
         r = wide_tile_launch<EXACT>(e, s, P, channels, pick.bt, hd, hf, 0, true, &pick.occ);
         if (r != AZG_OK) return r;
     } else {
+        // (no first-use allocation inside a capture, so no tile can be set up there: the set-up call comes first)
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(s, &cs);
-        const bool capturing = cs != hipStreamCaptureStatusNone;
+        if (cs != hipStreamCaptureStatusNone)
+            return fail(AZG_E_INVALID_ARG, "persistent wide-head search: call it once with sims == 0 (one-time set-up) before capturing it in a graph");
         int occ[4] = {0, 0, 0, 0};
         for (int t = 1; t <= tmax; t++) {                        // set up every tile this network fits; its occupancy on this device
             int o = 0;
-            if (capturing) {                                     // (no first-use allocation inside a capture: a tile that was never set up is left out)
-                continue;
-            }
             if (wide_tile_launch<EXACT>(e, s, P, channels, t, hd, hf, 0, true, &o) == AZG_OK) occ[t - 1] = o;
-        }
-        if (capturing) {                                         // a captured launch without a set-up call before it: the model over what is set up
-            return fail(AZG_E_INVALID_ARG, "persistent wide-head search: call it once with sims == 0 (one-time set-up) before capturing it in a graph");
         }
         bool any = false;
         for (int t = 0; t < tmax; t++) any |= occ[t] > 0;
@@ -1325,10 +1361,10 @@ template <bool EXACT>
 static int search_wide(azg_engine *e, void *stream, const void *w, const float *bias, const float *pre_scale, const float *pre_shift, int nblocks, int channels,
                        const void *head1_w, const float *head1_b, const HeadRows &hd, const HeadsFull &hf, int feat_k, int sims) {
     if (!e || !w || !bias || !head1_w || !head1_b || nblocks < 0 || sims < 0) return fail(AZG_E_INVALID_ARG, "null or out-of-range argument");
-    if (nblocks > 0 && (!pre_scale || !pre_shift)) return fail(AZG_E_INVALID_ARG, "pre_scale/pre_shift required");
+    if (int r = check_affine(nblocks, pre_scale, pre_shift)) return r;
     if (e->v.arena) return fail(AZG_E_UNSUPPORTED, "the persistent search launches are built for self-play engines");
-    const int A = e->gi.action_size, NV = e->gi.num_players + 1, hw = e->gi.obs_h * e->gi.obs_w;
-    if (feat_k != (hw * 16 + 31) / 32 * 32) return fail(AZG_E_INVALID_ARG, "feat_k must be H*W*16 rounded up to 32");
+    const int A = e->gi.action_size, NV = e->gi.num_players + 1;
+    if (int r = check_search_feat_k(e, feat_k)) return r;
     if (wide_max_tile(e->cfg.game, channels) == 0)
         return fail(AZG_E_UNSUPPORTED, "persistent wide-head search: built for the pairs azg_launch_support gives AZG_SUPPORT_SEARCH_WIDE (use azg_select / network / azg_backup)");
 #define AZG_NO_SPARSE(G, ...) \
@@ -1346,10 +1382,9 @@ static int search_wide(azg_engine *e, void *stream, const void *w, const float *
     int r = wide_tile_pick<EXACT>(e, s, P, channels, hd, hf, sims == 0, pick);
     if (r != AZG_OK) return r;
     if (sims == 0) return AZG_OK;                            // one-time set-up only
-    EvPair ep; const bool prof = netprof_begin(s, ep);
+    NetProfScope timed(s, 2);
     r = wide_tile_launch<EXACT>(e, s, P, channels, pick.bt, hd, hf, sims, false, nullptr);
-    if (r == AZG_E_UNSUPPORTED) { g_kev = nullptr; return fail(r, "persistent wide-head search: no such tile for this game / width"); }
-    netprof_end(s, 2, prof, ep);
+    if (r == AZG_E_UNSUPPORTED) return fail(r, "persistent wide-head search: no such tile for this game / width");
     return r;
 }
 
@@ -1358,8 +1393,7 @@ static int search_wide(azg_engine *e, void *stream, const void *w, const float *
 // measurement in ns per trial launch for 1 / 2 / 3 / 4 games per workgroup (0: not measured)}; AZG_E_INVALID_ARG before the first call of the
 // launch for this (engine size, depth)
 extern "C" int azg_search_wide_tile_info(azg_engine *e, int channels, int nblocks, int exact, int32_t *info12) {
-    int32_t *info8 = info12;
-    if (!e || !info8) return fail(AZG_E_INVALID_ARG, "null argument");
+    if (!e || !info12) return fail(AZG_E_INVALID_ARG, "null argument");
     int dev = 0, cus = 1;
     HIPCHK(hipGetDevice(&dev));
     int r = device_cus(&cus); if (r != AZG_OK) return r;
@@ -1367,9 +1401,9 @@ extern "C" int azg_search_wide_tile_info(azg_engine *e, int channels, int nblock
     auto it = g_tile.find(WideTileKey{dev, e->cfg.game, channels, exact ? 1 : 0, e->v.B, nblocks});
     if (it == g_tile.end()) return fail(AZG_E_INVALID_ARG, "no persistent wide-head launch has been set up for this engine size and depth");
     const WideTilePick &p = it->second;
-    info8[0] = p.bt; info8[1] = (e->v.B + p.bt - 1) / p.bt; info8[2] = p.occ; info8[3] = cus; info8[4] = p.source;
-    info8[5] = TRIAL_SIMS; info8[6] = info8[7] = 0;
-    for (int t = 0; t < 4; t++) info8[8 + t] = (int32_t)(p.us[t] * 1e3f);
+    info12[0] = p.bt; info12[1] = (e->v.B + p.bt - 1) / p.bt; info12[2] = p.occ; info12[3] = cus; info12[4] = p.source;
+    info12[5] = TRIAL_SIMS; info12[6] = info12[7] = 0;
+    for (int t = 0; t < 4; t++) info12[8 + t] = (int32_t)(p.us[t] * 1e3f);
     return AZG_OK;
 }
 
@@ -1413,8 +1447,8 @@ extern "C" int azg_search_arena_wide_exact_f16(azg_engine *e, void *stream, int 
         return fail(AZG_E_UNSUPPORTED, "the persistent wide arena launch is built for arena engines on the pairs azg_launch_support gives "
                                        "AZG_SUPPORT_SEARCH_WIDE (use azg_select / network / azg_backup)");
     if (nmodels < e->gi.num_players || nmodels > 4) return fail(AZG_E_INVALID_ARG, "one model per player, at most 4");
-    const int A = e->gi.action_size, NV = e->gi.num_players + 1, hw = e->gi.obs_h * e->gi.obs_w;
-    if (feat_k != (hw * 16 + 31) / 32 * 32) return fail(AZG_E_INVALID_ARG, "feat_k must be H*W*16 rounded up to 32");
+    const int A = e->gi.action_size, NV = e->gi.num_players + 1;
+    if (int r = check_search_feat_k(e, feat_k)) return r;
     WideArenaArgs sa0{};
     sa0.ev = e->v; sa0.sims = sims; sa0.hd = HeadRows{nullptr, nullptr, feat_k}; sa0.seat_of_slot = seat_of_slot; sa0.nmodels = nmodels;
     int real = -1;
@@ -1429,23 +1463,19 @@ extern "C" int azg_search_arena_wide_exact_f16(azg_engine *e, void *stream, int 
             if (real < 0) real = m;
         }
     }
-    if (p2i_host) for (int i = 0; i < e->gi.num_players && i < 8; i++) {
-        if (p2i_host[i] < 0 || p2i_host[i] >= nmodels) return fail(AZG_E_INVALID_ARG, "player_to_index entry out of range");
-        sa0.seat.v[i] = p2i_host[i];
-    }
+    if (int r = seat_map(e, p2i_host, nmodels, sa0.seat)) return r;
     // (P: the shape of the launch -- boards, depth, heads form; the parameters every workgroup reads are its model's, sa.m)
     const WideModel &M0 = sa0.m[real < 0 ? 0 : real];
     TowerParams P = tower_params(nullptr, M0.w, M0.bias, M0.pre_scale, M0.pre_shift, e->v.B, nblocks);
     set_fact_heads(P, M0.head1_w, M0.head1_b, nullptr, feat_k); P.A = A; P.NV = NV;
     hipStream_t s = (hipStream_t)stream;
     const bool init = sims == 0;                                  // sims == 0: set up only
-    EvPair ep; const bool prof = !init && netprof_begin(s, ep);
+    NetProfScope timed(s, 2, !init);
     int r = AZG_E_UNSUPPORTED;
 #define AZG_ROW(G, C, BT, PS, MINB, KS) if (BT == 1 && game == G::ID && channels == C) r = wide_arena_tile<G, C, BT, PS, MINB, KS>(s, P, sa0, init);
     AZG_WIDE_TILES(AZG_ROW)
 #undef AZG_ROW
-    if (r == AZG_E_UNSUPPORTED) { g_kev = nullptr; return fail(r, "persistent wide arena launch: no tile for this game / width"); }
-    if (!init) netprof_end(s, 2, prof, ep);
+    if (r == AZG_E_UNSUPPORTED) return fail(r, "persistent wide arena launch: no tile for this game / width");
     return r;
 }
 
@@ -1455,10 +1485,11 @@ extern "C" int azg_policy_value_heads_f16(void *stream, const void *y, const voi
     if (boards <= 0 || k <= 0 || (k & 31) || A <= 0 || A > 1024 || NV <= 0 || NV > 64) return fail(AZG_E_INVALID_ARG, "boards > 0, k a multiple of 32, 0 < A <= 1024, 0 < NV <= 64");
     const int osub = (A + NV + 15) / 16, nchunks = (osub + HEAD_NS - 1) / HEAD_NS, groups = (boards + 15) / 16;
     hipStream_t s = (hipStream_t)stream;
-    EvPair ep; const bool prof = netprof_begin(s, ep);
-    AZG_LAUNCH(k_heads, dim3(groups * nchunks), dim3(HEAD_WAVES * 64), 0, s, (const _Float16 *)y, (const half8 *)head_w_packed, head_b, logits_ws,
-                       boards, k / 32, osub);
-    netprof_end(s, 1, prof, ep);
+    {
+        NetProfScope timed(s, 1);                            // (the GEMM alone: the softmax below is not timed)
+        AZG_LAUNCH(k_heads, dim3(groups * nchunks), dim3(HEAD_WAVES * 64), 0, s, (const _Float16 *)y, (const half8 *)head_w_packed, head_b, logits_ws,
+                           boards, k / 32, osub);
+    }
     if (policy)                                              // (NULL: leave the logits for azg_backup_select_logits)
         AZG_LAUNCH(k_heads_softmax, dim3((boards + 3) / 4), dim3(256), 0, s, (const float *)logits_ws, policy, value, boards, osub * 16, A, NV);
     HIPCHK(hipGetLastError());
@@ -1471,10 +1502,11 @@ extern "C" int azg_policy_value_heads_fact_f16(void *stream, const void *feat, c
     if (boards <= 0 || feat_k <= 0 || (feat_k & 31) || A <= 0 || A > 1024 || NV <= 0 || NV > 16) return fail(AZG_E_INVALID_ARG, "boards > 0, feat_k a multiple of 32, 0 < A <= 1024, 0 < NV <= 16");
     const int osp = (A + 15) / 16, osub = (A + NV + 15) / 16, nchunks = (osp + HEADF_NS - 1) / HEADF_NS + 1, groups = (boards + 15) / 16;
     hipStream_t s = (hipStream_t)stream;
-    EvPair ep; const bool prof = netprof_begin(s, ep);
     const HeadsFact hf{(const half8 *)wp_packed, (const half8 *)wv_packed, head_b, feat_k, osp, A, NV};
-    AZG_LAUNCH(k_heads_fact, dim3(groups * nchunks), dim3(HEADF_Q * 64), 0, s, (const _Float16 *)feat, hf, logits_ws, boards, osub * 16);
-    netprof_end(s, 1, prof, ep);
+    {
+        NetProfScope timed(s, 1);                            // (the GEMM alone: the softmax below is not timed)
+        AZG_LAUNCH(k_heads_fact, dim3(groups * nchunks), dim3(HEADF_Q * 64), 0, s, (const _Float16 *)feat, hf, logits_ws, boards, osub * 16);
+    }
     if (policy)
         AZG_LAUNCH(k_heads_softmax, dim3((boards + 3) / 4), dim3(256), 0, s, (const float *)logits_ws, policy, value, boards, osub * 16, A, NV);
     HIPCHK(hipGetLastError());
@@ -1586,14 +1618,11 @@ extern "C" int azg_debug_tree_timing(azg_engine *e, unsigned long long *host) {
 
 extern "C" int azg_profile_enable(azg_engine *e, int on) {
     if (!e) return fail(AZG_E_INVALID_ARG, "null engine");
-    prof_drain(e);
-    e->profile = on != 0;
-    if (on) { for (int f = 0; f < 3; f++) { e->ms[f] = 0; e->launches[f] = 0; } }
+    e->prof.enable(on != 0);
     return AZG_OK;
 }
 extern "C" int azg_profile_read(azg_engine *e, double *ms3, int64_t *launches3) {
     if (!e || !ms3 || !launches3) return fail(AZG_E_INVALID_ARG, "null argument");
-    prof_drain(e);
-    for (int f = 0; f < 3; f++) { ms3[f] = e->ms[f]; launches3[f] = e->launches[f]; }
+    e->prof.read(ms3, launches3);
     return AZG_OK;
 }

@@ -15,9 +15,10 @@ namespace azg {
 // per CU of the device because that is what was measured (256 CUs: 640 / 1280 boards = 2.5 / 5 per CU).  The big tile has the least
 // MFMA padding, small ones fill the chip at small batches (the arena, the single-tree API, brandubh's 512 games per GPU).  TILE_REST
 // marks the pair's last default row (every larger batch); TILE_NEVER a row no batch size takes by default -- a measured alternative
-// that an override of a tuning build reaches.  The three connect4 x 128 rows without a split are also the tiles of the fused search
-// launches (azg_search_f16 at the same limits, azg_search_arena_f16).
+// that an override of a tuning build reaches.  The rows is_fused_search_tile names are also the tiles of the fused search launches
+// (azg_search_f16 at the same limits; azg_search_arena_f16: the one-board row).
 constexpr int TILE_NEVER = 0, TILE_REST = 1 << 30;
+template <class G, int C, int PS, int KS> constexpr bool is_fused_search_tile = G::ID == C4::ID && C == 128 && PS == 1 && KS == 1;   // connect4 x 128 without a split
 #ifdef AZG_TUNING
 #define AZG_TOWER_TILES_TUNING(X) \
     X(C4, 128, 2, 2, 1, TILE_NEVER)   /* (sweep only: profiles/r03_arena_tile_sweep.txt) */
@@ -167,14 +168,14 @@ template <class G> constexpr bool has_sparse_heads = G::SPARSE_HEADS;
 // azg_launch_support: the AZG_SUPPORT_* mask of (game, tower width); 0 for a game id the lists do not know
 inline int tile_support(int game, int channels) {
     int m = 0;
-#define AZG_ROW(G, C, BT, PS, KS, LIMIT) if (game == G::ID && channels == C) m |= AZG_SUPPORT_TOWER;
+#define AZG_ROW(G, C, BT, PS, KS, LIMIT) \
+    if (game == G::ID && channels == C) m |= AZG_SUPPORT_TOWER | (is_fused_search_tile<G, C, PS, KS> ? AZG_SUPPORT_SEARCH_FUSED : 0);
     AZG_TOWER_TILES(AZG_ROW)
 #undef AZG_ROW
 #define AZG_ROW(G, C, BT, PS, MINB, KS) \
     if (game == G::ID && channels == C) m |= AZG_SUPPORT_SEARCH_WIDE | (has_sparse_heads<G> ? AZG_SUPPORT_SEARCH_SPARSE : 0);
     AZG_WIDE_TILES(AZG_ROW)
 #undef AZG_ROW
-    if (game == AZG_GAME_CONNECT4 && channels == 128) m |= AZG_SUPPORT_SEARCH_FUSED;   // azg_search_f16 / azg_search_arena_f16: one special case
     return m;
 }
 

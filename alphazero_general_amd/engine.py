@@ -10,15 +10,8 @@ import numpy as np
 import torch
 
 from . import _abi
+from ._abi import ptr as _ptr, stream as _stream
 from .utils import default_temp_scaling, temp_table
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 class DeviceEngine:

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from ._abi import ptr as _ptr, stream as _stream
 from .Game import azg_game_id
 
 STATE_BYTES = C.sizeof(_abi.State)                              # 80
@@ -21,14 +22,6 @@ Step = collections.namedtuple('Step', 'next valid win obs status')
 Symmetries = collections.namedtuple('Symmetries', 'states obs pi')
 Choice = collections.namedtuple('Choice', 'actions status')
 _OBS_FORMS = {torch.float32: 0, torch.float16: 1, 'nhwc8': 2}
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 class DeviceGames:

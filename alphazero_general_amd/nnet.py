@@ -5,11 +5,15 @@ probabilities.  The network stays PyTorch-ROCm (MIOpen / hipBLASLt -> MFMA); wha
 eval-mode BatchNorm folded into the convolutions, channels-last fp16, softmax epilogue in fp32, and optional
 hipGraph capture at a fixed batch size.  Training is out of scope.
 """
+import ctypes
+
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _abi
+from ._abi import ptr, stream
 from .utils import dotdict
 
 DEFAULT_NET_ARGS = dotdict(num_channels=32, depth=4, value_head_channels=16, policy_head_channels=16,
@@ -225,19 +229,15 @@ class HipResNet:
     def profile(on=True):
         """HIP-event timing of every network launch of this process, recorded by the library on the launch stream
         (azg_profile_net_enable); read with profile_read()."""
-        from . import _abi
         _abi.check(_abi.lib().azg_profile_net_enable(int(on)))
 
     @staticmethod
     def profile_read():
-        import ctypes as C
-        from . import _abi
-        ms = (C.c_double * 3)(); n = (C.c_int64 * 3)()
+        ms = (ctypes.c_double * 3)(); n = (ctypes.c_int64 * 3)()
         _abi.check(_abi.lib().azg_profile_net_read(ms, n))
         return dict(tower_ms=ms[0], heads_ms=ms[1], search_ms=ms[2], tower_n=n[0], heads_n=n[1], search_n=n[2])
 
     def __init__(self, folded: FoldedResNet, game_id, device):
-        from . import _abi
         self.L, self.game, self.device = _abi.lib(), int(game_id), torch.device(device)
         self._check = _abi.check
         C, H, W = folded.shape
@@ -358,43 +358,44 @@ class HipResNet:
         assert self.wide_head
         return self.forward_nhwc8(x, key, logits_only=True)
 
+    def _tower(self):
+        """the five tower arguments every launch of this network passes: weights, biases, the blocks' affines, depth"""
+        return ptr(self.tower_w), ptr(self.tower_b), ptr(self.tower_ps), ptr(self.tower_pt), len(self.blocks)
+
+    def _features(self, x, key):
+        """tower + the two 1x1 head convolutions, ONE launch: x [B, H*W, 8] fp16 -> head features [B, 2 * feat_k] fp16 (scratch of `key`)"""
+        B = x.shape[0]
+        feat = self._scratch('feat', key, B, lambda n: (torch.zeros((n, 2 * self.feat_k), dtype=torch.float16, device=self.device),))[0][:B]
+        w, b, ps, pt, nb = self._tower()
+        self._check(self.L.azg_resnet_tower_features_f16(stream(), self.game, ptr(x), w, b, ps, pt, int(B), nb, int(self.CH), ptr(self.head1_w),
+                                                         ptr(self.head1_b), ptr(feat), int(self.feat_k)))
+        return feat
+
     def forward_nhwc8(self, x, key=0, logits_only=False):
         """x: [B, H*W, 8] fp16 -> (policy [B, A], value [B, P+1]) float32 probabilities.  `key` selects a private set
         of activation buffers (one per captured graph, so that graphs on different streams never share scratch)."""
         B = x.shape[0]
+        w, b, ps, pt, nb = self._tower()
         if self.fused_head and not logits_only:                  # tower + heads + softmax in ONE launch
-            import ctypes as C
-            vp = lambda q: C.c_void_p(q.data_ptr())
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             pol, val = [t[:B] for t in self._scratch('pv', key, B, lambda n: (
                 torch.empty((n, self.A), dtype=torch.float32, device=self.device),
                 torch.empty((n, self.NV), dtype=torch.float32, device=self.device)))]
-            self._check(self.L.azg_resnet_policy_value_f16(st, self.game, vp(x), vp(self.tower_w), vp(self.tower_b), vp(self.tower_ps),
-                                                           vp(self.tower_pt), int(B), len(self.blocks), vp(self.head_w_packed),
-                                                           vp(self.head_b16), int(self.A), int(self.NV), vp(pol), vp(val)))
+            self._check(self.L.azg_resnet_policy_value_f16(stream(), self.game, ptr(x), w, b, ps, pt, int(B), nb, ptr(self.head_w_packed),
+                                                           ptr(self.head_b16), int(self.A), int(self.NV), ptr(pol), ptr(val)))
             return pol, val
-        import ctypes as C
-        vp = lambda q: C.c_void_p(q.data_ptr())
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         pol, val, ws = [t[:B] for t in self._scratch('pvw', key, B, lambda n: tuple(
-            torch.empty((n, w), dtype=torch.float32, device=self.device) for w in (self.A, self.NV, self.head_opad)))]
-        null = C.c_void_p(0)
+            torch.empty((n, k), dtype=torch.float32, device=self.device) for k in (self.A, self.NV, self.head_opad)))]
+        out = (None, None) if logits_only else (ptr(pol), ptr(val))
         if self.fact_head:                                       # tower + 1x1 head convs: one launch; collapsed dense chains: one more
-            feat = self._scratch('feat', key, B, lambda n: (torch.zeros((n, 2 * self.feat_k), dtype=torch.float16, device=self.device),))[0][:B]
-            self._check(self.L.azg_resnet_tower_features_f16(st, self.game, vp(x), vp(self.tower_w), vp(self.tower_b), vp(self.tower_ps),
-                                                             vp(self.tower_pt), int(B), len(self.blocks), int(self.CH), vp(self.head1_w),
-                                                             vp(self.head1_b), vp(feat), int(self.feat_k)))
-            self._check(self.L.azg_policy_value_heads_fact_f16(st, vp(feat), vp(self.head2_wp), vp(self.head2_wv), vp(self.head2_b), int(B),
-                                                               int(self.feat_k), int(self.A), int(self.NV), vp(ws),
-                                                               null if logits_only else vp(pol), null if logits_only else vp(val)))
+            feat = self._features(x, key)
+            self._check(self.L.azg_policy_value_heads_fact_f16(stream(), ptr(feat), ptr(self.head2_wp), ptr(self.head2_wv), ptr(self.head2_b), int(B),
+                                                               int(self.feat_k), int(self.A), int(self.NV), ptr(ws), *out))
             return ws if logits_only else (pol, val)
         s = self._buffers(B, key)                                # tower: one persistent launch, activations resident in LDS
-        self._check(self.L.azg_resnet_tower_f16(st, self.game, vp(x), vp(self.tower_w), vp(self.tower_b), vp(self.tower_ps),
-                                                vp(self.tower_pt), vp(s), int(B), len(self.blocks), int(self.CH)))
+        self._check(self.L.azg_resnet_tower_f16(stream(), self.game, ptr(x), w, b, ps, pt, ptr(s), int(B), nb, int(self.CH)))
         # fully collapsed heads GEMM + both softmaxes: two launches (or one, stopping at the logits)
-        self._check(self.L.azg_policy_value_heads_f16(st, vp(s), vp(self.head_w_wide), vp(self.head_b_wide), int(B), self.HW * self.CH,
-                                                      int(self.A), int(self.NV), vp(ws), null if logits_only else vp(pol),
-                                                      null if logits_only else vp(val)))
+        self._check(self.L.azg_policy_value_heads_f16(stream(), ptr(s), ptr(self.head_w_wide), ptr(self.head_b_wide), int(B), self.HW * self.CH,
+                                                      int(self.A), int(self.NV), ptr(ws), *out))
         return ws if logits_only else (pol, val)
 
     def forward_features_nhwc8(self, x, key=0):
@@ -402,22 +403,13 @@ class HipResNet:
         convolutions, ONE launch), for DeviceEngine.backup_select_features, which applies the collapsed Linear chains itself --
         only to the valid actions of every leaf."""
         assert self.fact_head
-        import ctypes as C
-        vp = lambda q: C.c_void_p(q.data_ptr())
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        B = x.shape[0]
-        feat = self._scratch('feat', key, B, lambda n: (torch.zeros((n, 2 * self.feat_k), dtype=torch.float16, device=self.device),))[0][:B]
-        self._check(self.L.azg_resnet_tower_features_f16(st, self.game, vp(x), vp(self.tower_w), vp(self.tower_b), vp(self.tower_ps),
-                                                         vp(self.tower_pt), int(B), len(self.blocks), int(self.CH), vp(self.head1_w),
-                                                         vp(self.head1_b), vp(feat), int(self.feat_k)))
-        return feat
+        return self._features(x, key)
 
     @property
     def can_search(self):
         """a persistent search launch exists for this network: fused heads (azg_search_f16) or factorised heads (azg_search_wide_exact_f16,
         and azg_search_wide_f16 where the pair has sparse heads) on a (game, tower width) the library instantiates it for --
         azg_launch_support answers from the library's own tile lists."""
-        from . import _abi
         m = _abi.launch_support(self.game, self.CH)
         return bool((self.fused_head and m & _abi.SUPPORT_SEARCH_FUSED) or (self.fact_head and m & _abi.SUPPORT_SEARCH_WIDE))
 
@@ -440,20 +432,14 @@ class HipResNet:
         of each leaf's valid actions (sparse heads: equal to rounding).  Fused heads (connect4) are always exact."""
         if not self.can_search:
             raise NotImplementedError('no persistent search launch for this (game, network) -- use select / network / backup')
-        import ctypes as C
-        vp = lambda q: C.c_void_p(q.data_ptr())
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         if self.fused_head:
-            self._check(self.L.azg_search_f16(engine.h, st, vp(self.tower_w), vp(self.tower_b), vp(self.tower_ps), vp(self.tower_pt),
-                                              len(self.blocks), vp(self.head_w_packed), vp(self.head_b16), int(sims)))
+            self._check(self.L.azg_search_f16(engine.h, stream(), *self._tower(), ptr(self.head_w_packed), ptr(self.head_b16), int(sims)))
         elif exact:
-            self._check(self.L.azg_search_wide_exact_f16(engine.h, st, vp(self.tower_w), vp(self.tower_b), vp(self.tower_ps), vp(self.tower_pt),
-                                                         len(self.blocks), int(self.CH), vp(self.head1_w), vp(self.head1_b), vp(self.head2_wps),
-                                                         vp(self.head2_wv), vp(self.head2_b), int(self.feat_k), int(sims)))
+            self._check(self.L.azg_search_wide_exact_f16(engine.h, stream(), *self._tower(), int(self.CH), ptr(self.head1_w), ptr(self.head1_b),
+                                                         ptr(self.head2_wps), ptr(self.head2_wv), ptr(self.head2_b), int(self.feat_k), int(sims)))
         else:
-            self._check(self.L.azg_search_wide_f16(engine.h, st, vp(self.tower_w), vp(self.tower_b), vp(self.tower_ps), vp(self.tower_pt),
-                                                   len(self.blocks), int(self.CH), vp(self.head1_w), vp(self.head1_b), vp(self.head_rows),
-                                                   vp(self.head2_b), int(self.feat_k), int(sims)))
+            self._check(self.L.azg_search_wide_f16(engine.h, stream(), *self._tower(), int(self.CH), ptr(self.head1_w), ptr(self.head1_b),
+                                                   ptr(self.head_rows), ptr(self.head2_b), int(self.feat_k), int(sims)))
 
     def search_tile(self, engine, exact=False):
         """the tile the persistent wide-head launch runs `engine` with (azg_search_wide_tile_info): dict(games_per_workgroup, workgroups,
@@ -461,8 +447,7 @@ class HipResNet:
         fused-head networks (connect4 x 128: the tile follows the engine's size alone) or before the launch's first call."""
         if not (self.fact_head and self.can_search):
             return None
-        import ctypes as C
-        info = (C.c_int32 * 12)()
+        info = (ctypes.c_int32 * 12)()
         if self.L.azg_search_wide_tile_info(engine.h, int(self.CH), len(self.blocks), int(bool(exact)), info) != 0:
             return None
         return dict(games_per_workgroup=int(info[0]), workgroups=int(info[1]), workgroups_per_cu=int(info[2]), cus=int(info[3]),
@@ -485,50 +470,49 @@ class HipResNet:
         return dict(tower=tower, heads=head, total=tower + head)
 
     @staticmethod
+    def _model_arrays(nets, *names):
+        """per name one c_void_p array over `nets`: the address of every network's tensor of that name, null for a None entry (a raw seat)"""
+        return [(ctypes.c_void_p * len(nets))(*[None if n is None else getattr(n, name).data_ptr() for n in nets]) for name in names]
+
+    @staticmethod
+    def _seating(player_to_index, slot_seats):
+        """the two seating arguments of the arena launches: the host's player -> model list and / or the per-slot seats on the device"""
+        p2i = None if player_to_index is None else (ctypes.c_int32 * len(player_to_index))(*[int(x) for x in player_to_index])
+        return p2i, ptr(slot_seats)
+
+    @staticmethod
     def forward_models(nets, x_all, policy_all, value_all, rows_per_model):
         """Arena evaluation in ONE launch without a host read of the batch split: nets[m] (HipResNets of one architecture)
         evaluates rows [sum(rows_per_model[:m]), + rows_per_model[m]) of x_all [B, H*W, 8] into policy_all / value_all
         (rows_per_model: int32 device tensor from DeviceEngine.arena_rows).  Needs the fused tower + heads kernel."""
-        import ctypes as C
         n0 = nets[0]
         for n in nets:
             if not n.fused_head:
                 raise NotImplementedError('multi-model launches need the fused tower + heads kernel (128 channels, A + NV <= 16)')
             assert (n.game, n.CH, len(n.blocks), n.A, n.NV) == (n0.game, n0.CH, len(n0.blocks), n0.A, n0.NV)
-        arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        vp = lambda q: C.c_void_p(q.data_ptr())
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        n0._check(n0.L.azg_resnet_policy_value_multi_f16(
-            st, n0.game, vp(x_all), len(nets), arr([n.tower_w for n in nets]), arr([n.tower_b for n in nets]),
-            arr([n.tower_ps for n in nets]), arr([n.tower_pt for n in nets]), int(x_all.shape[0]), len(n0.blocks),
-            arr([n.head_w_packed for n in nets]), arr([n.head_b16 for n in nets]), int(n0.A), int(n0.NV), vp(policy_all), vp(value_all),
-            vp(rows_per_model)))
+        w, b, ps, pt, hw, hb = HipResNet._model_arrays(nets, 'tower_w', 'tower_b', 'tower_ps', 'tower_pt', 'head_w_packed', 'head_b16')
+        n0._check(n0.L.azg_resnet_policy_value_multi_f16(stream(), n0.game, ptr(x_all), len(nets), w, b, ps, pt, int(x_all.shape[0]), len(n0.blocks),
+                                                         hw, hb, int(n0.A), int(n0.NV), ptr(policy_all), ptr(value_all), ptr(rows_per_model)))
 
     @staticmethod
     def search_arena(nets, engine, sims, player_to_index=None, slot_seats=None):
         """a whole arena move in ONE persistent launch (azg_search_arena_f16): every game of `engine` (an arena engine) is searched
         `sims` simulations on its mover's tree with its mover's model -- nets[player_to_index[mover]], or the slot's own seating
         (slot_seats: int32 device tensor, 4 bits per player).  Needs the fused tower + heads kernel on every model."""
-        import ctypes as C
         n0 = nets[0]
         for n in nets:
             if not n.fused_head or n.game != 0 or n.CH != 128:
                 raise NotImplementedError('the persistent arena launch needs connect4 models with the fused tower + heads kernel (128 channels)')
             assert (len(n.blocks), n.A, n.NV) == (len(n0.blocks), n0.A, n0.NV)
-        arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        p2i = None if player_to_index is None else (C.c_int32 * len(player_to_index))(*[int(x) for x in player_to_index])
-        seats = None if slot_seats is None else C.c_void_p(slot_seats.data_ptr())
-        n0._check(n0.L.azg_search_arena_f16(engine.h, st, len(nets), arr([n.tower_w for n in nets]), arr([n.tower_b for n in nets]),
-                                            arr([n.tower_ps for n in nets]), arr([n.tower_pt for n in nets]), len(n0.blocks),
-                                            arr([n.head_w_packed for n in nets]), arr([n.head_b16 for n in nets]), p2i, seats, int(sims)))
+        w, b, ps, pt, hw, hb = HipResNet._model_arrays(nets, 'tower_w', 'tower_b', 'tower_ps', 'tower_pt', 'head_w_packed', 'head_b16')
+        n0._check(n0.L.azg_search_arena_f16(engine.h, stream(), len(nets), w, b, ps, pt, len(n0.blocks), hw, hb,
+                                            *HipResNet._seating(player_to_index, slot_seats), int(sims)))
 
     @staticmethod
     def search_arena_wide(nets, engine, sims, player_to_index=None, slot_seats=None):
         """search_arena for factorised-head networks (azg_search_arena_wide_exact_f16: the pairs with `can_search`, exact heads -- the
         bits NNetWrapper.process returns).  A None entry of `nets` is a raw seat: RawMCTSPlayer.process's constants (policy float32(1 / A),
         value zeros), no network runs for its games.  The real models must share (game, tower width, depth, feat_k)."""
-        import ctypes as C
         real = [n for n in nets if n is not None]
         if not real:
             raise ValueError('the wide arena launch needs at least one network')
@@ -537,23 +521,17 @@ class HipResNet:
             if not (n.fact_head and n.can_search):
                 raise NotImplementedError('the persistent wide arena launch needs factorised-head networks the persistent search supports')
             assert (n.game, n.CH, len(n.blocks), n.feat_k, n.A, n.NV) == (n0.game, n0.CH, len(n0.blocks), n0.feat_k, n0.A, n0.NV)
-        arr = lambda f: (C.c_void_p * len(nets))(*[0 if n is None else f(n).data_ptr() for n in nets])
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        p2i = None if player_to_index is None else (C.c_int32 * len(player_to_index))(*[int(x) for x in player_to_index])
-        seats = None if slot_seats is None else C.c_void_p(slot_seats.data_ptr())
-        n0._check(n0.L.azg_search_arena_wide_exact_f16(
-            engine.h, st, len(nets), arr(lambda n: n.tower_w), arr(lambda n: n.tower_b), arr(lambda n: n.tower_ps), arr(lambda n: n.tower_pt),
-            len(n0.blocks), int(n0.CH), arr(lambda n: n.head1_w), arr(lambda n: n.head1_b), arr(lambda n: n.head2_wps),
-            arr(lambda n: n.head2_wv), arr(lambda n: n.head2_b), int(n0.feat_k), p2i, seats, int(sims)))
+        w, b, ps, pt, h1w, h1b, wps, wv, hb = HipResNet._model_arrays(nets, 'tower_w', 'tower_b', 'tower_ps', 'tower_pt', 'head1_w', 'head1_b',
+                                                                      'head2_wps', 'head2_wv', 'head2_b')
+        n0._check(n0.L.azg_search_arena_wide_exact_f16(engine.h, stream(), len(nets), w, b, ps, pt, len(n0.blocks), int(n0.CH), h1w, h1b, wps, wv, hb,
+                                                       int(n0.feat_k), *HipResNet._seating(player_to_index, slot_seats), int(sims)))
 
     def to_nhwc8(self, batch):
         """[B, C, H, W] (any float dtype) -> [B, H*W, 8] fp16."""
         B, C = batch.shape[0], batch.shape[1]
         if batch.dtype == torch.float32 and batch.is_cuda and batch.is_contiguous() and B > 0:      # one launch (azg_obs_to_nhwc8_f16)
-            import ctypes as Ct
             x = torch.empty((B, self.HW, 8), dtype=torch.float16, device=self.device)
-            self._check(self.L.azg_obs_to_nhwc8_f16(Ct.c_void_p(torch.cuda.current_stream().cuda_stream), Ct.c_void_p(batch.data_ptr()), int(B), int(C),
-                                                    int(self.HW), Ct.c_void_p(x.data_ptr())))
+            self._check(self.L.azg_obs_to_nhwc8_f16(stream(), ptr(batch), int(B), int(C), int(self.HW), ptr(x)))
             return x
         x = torch.zeros((B, self.HW, 8), dtype=torch.float16, device=self.device)
         x[:, :, :C] = batch.to(self.device).reshape(B, C, self.HW).permute(0, 2, 1)
@@ -681,7 +659,6 @@ class NNetWrapper:
         if self.device.type == 'cuda':
             net = net.to(memory_format=torch.channels_last)
         self._infer, self._graph, self._hip = net.eval(), None, None
-        from . import _abi
         use_hip = self.backend == 'hip' or (self.backend == 'auto' and self.device.type == 'cuda'
                                             and _abi.launch_support(getattr(self.game_cls, 'AZG_GAME_ID', None), self.args.num_channels)
                                             & _abi.SUPPORT_TOWER)

@@ -559,6 +559,10 @@ class ArenaRunner:
         HipResNet.search_arena_wide([None if n is None else n._hip for n in self.nnets], self.engine, sims,
                                     None if self.slot_seats is not None else self.player_to_index, self.slot_seats)
 
+    def _search_fused(self, sims):
+        HipResNet.search_arena([n._hip for n in self.nnets], self.engine, sims,
+                               None if self.slot_seats is not None else self.player_to_index, self.slot_seats)
+
     def _round_device_split(self, sims):
         """A whole move: the mover of every game -- hence the row <-> game map and the per-model split -- is fixed until
         advance, so the rows are laid out once; then select, and per simulation ONE tower launch for all models plus one
@@ -569,7 +573,7 @@ class ArenaRunner:
             e.advance(record_history=False)
             return
         if self.fused_search:
-            HipResNet.search_arena([n._hip for n in self.nnets], e, sims, None if self.slot_seats is not None else self.player_to_index, self.slot_seats)
+            self._search_fused(sims)
             e.advance(record_history=False)
             return
         row_of_slot, rpm = self._rows()
@@ -591,7 +595,7 @@ class ArenaRunner:
         else:
             self._step_device_split()                                # warm: lazy allocations happen outside the capture
         if self.fused_search:
-            HipResNet.search_arena([n._hip for n in self.nnets], self.engine, 0, None if self.slot_seats is not None else self.player_to_index, self.slot_seats)
+            self._search_fused(0)                                    # one-time set-up outside the capture
         self.engine.reset()                                          # (the warm step is not part of any game)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
