@@ -102,6 +102,9 @@ SYMBOLS = {
     'azg_game_step': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     'azg_game_choose': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'azg_game_symmetries': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'azg_game_lookahead': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    'azg_game_scripted_player': (C.c_char_p, [_i]),
+    'azg_game_choose_scripted': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     'azg_policy_value_heads_f16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'azg_tower_layout': (_i, [_i, _i, _i, _vp, _vp, _vp]),
     'azg_launch_support': (_i, [_i, _i]),

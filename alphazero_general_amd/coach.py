@@ -12,7 +12,8 @@ device when every player is a model player or the reference's RawMCTSPlayer (com
 575-584: a raw seat, evaluated on the device with RawMCTSPlayer.process's constants) of a game with device rules.  Everything else --
 train(), gating, checkpoints, the TensorBoard writer, compareToBaseline against other non-model players (RandomPlayer, unbatched
 arenas) -- runs the reference's code; native_coach(..., raw_seats=False) sends RawMCTSPlayer arenas there too, and
-native_coach(..., tree_free_seats=True) brings RandomPlayer / NNPlayer arenas, unbatched ones included, to the device.  No agent processes, no shared
+native_coach(..., tree_free_seats=True) brings RandomPlayer / NNPlayer arenas, unbatched ones included, to the device, and
+native_coach(..., scripted_seats=True) the games' scripted baseline players.  No agent processes, no shared
 tensors, no queues: the games live on the GPU(s) (iteration.run_iteration / run_arena), the live net's weights are adopted in
 memory (NNetWrapper.adopt), and the three sample files the unchanged Coach.train loads (:442-456) are written by rank 0.
 
@@ -54,9 +55,10 @@ class _NetCache:
         return w.adopt(ref_net)
 
 
-def native_coach(Coach, *, device=None, install_arena=True, raw_seats=True, tree_free_seats=False):
+def native_coach(Coach, *, device=None, install_arena=True, raw_seats=True, tree_free_seats=False, scripted_seats=False):
     """class factory: the reference's Coach with its self-play phase on the device engine (see the module docstring).  tree_free_seats:
-    native_arena's opt-in -- arenas against RandomPlayer / NNPlayer (compareToBaseline with such a baselineTester) on the device too."""
+    native_arena's opt-in -- arenas against RandomPlayer / NNPlayer (compareToBaseline with such a baselineTester) on the device too; scripted_seats: the same for
+    the scripted baseline players (is_scripted_player)."""
     cmod = sys.modules[Coach.__module__]
     TrainState = getattr(cmod, 'TrainState', None)
 
@@ -124,7 +126,7 @@ def native_coach(Coach, *, device=None, install_arena=True, raw_seats=True, tree
 
     NativeCoach.__name__ = NativeCoach.__qualname__ = 'Native' + Coach.__name__
     if install_arena and hasattr(cmod, 'Arena'):
-        cmod.Arena = native_arena(cmod.Arena, device=device, raw_seats=raw_seats, tree_free_seats=tree_free_seats)
+        cmod.Arena = native_arena(cmod.Arena, device=device, raw_seats=raw_seats, tree_free_seats=tree_free_seats, scripted_seats=scripted_seats)
     return NativeCoach
 
 
@@ -145,7 +147,22 @@ def tree_free_kind(p):
     return {'RandomPlayer': 'random', 'NNPlayer': 'policy'}.get(t.__name__)
 
 
-def native_arena(Arena, *, device=None, raw_seats=True, tree_free_seats=False):
+# the reference's scripted baseline players: (env package, module, class) -> the game id they belong to
+_SCRIPTED_PLAYERS = {('connect4', 'players', 'OneStepLookaheadConnect4Player'): 0, ('othello', 'OthelloPlayers', 'GreedyOthelloPlayer'): 3,
+                     ('gobang', 'GobangPlayers', 'GreedyGobangPlayer'): 4}
+
+
+def is_scripted_player(p, game_cls):
+    """the reference's OneStepLookaheadConnect4Player / GreedyOthelloPlayer / GreedyGobangPlayer themselves (envs/connect4/players.py:26-69,
+    envs/othello/OthelloPlayers.py:27-40, envs/gobang/GobangPlayers.py:27-40; recognised like tree_free_kind: module and class name, no
+    `play` of the instance's own) in an arena of THEIR game: played on the device by games.DeviceGames.choose_scripted"""
+    from .Game import azg_game_id
+    t = type(p)
+    gid = _SCRIPTED_PLAYERS.get(tuple(t.__module__.split('.')[-2:]) + (t.__name__,))
+    return gid is not None and 'play' not in vars(p) and has_device_rules(game_cls) and azg_game_id(game_cls) == gid
+
+
+def native_arena(Arena, *, device=None, raw_seats=True, tree_free_seats=False, scripted_seats=False):
     """class factory: the reference's Arena whose batched play_games runs on the device when it can (every player carries a model `.nn`
     or is a RawMCTSPlayer -- a raw seat; raw_seats=False: such arenas fall through --, Arena was built with use_batched_mcts, the game has
     device rules); anything else falls through to the reference's own code.
@@ -153,24 +170,28 @@ def native_arena(Arena, *, device=None, raw_seats=True, tree_free_seats=False):
     MCTSPlayer and RawMCTSPlayer, and an Arena built with use_batched_mcts=False -- what Coach.compareToBaseline builds for a
     RandomPlayer (Coach.py:577) -- takes the device path as well.  The MCTS seats then play with the BATCHED arena's settings
     (args.arenaTemp, no root noise / temperature, trees re-rooted every move), not MCTSPlayer.play's own startTemp schedule and
-    args.add_root_*: INTEGRATION.md section 3a."""
+    args.add_root_*: INTEGRATION.md section 3a.
+    scripted_seats=True (opt-in) seats the scripted baseline players of connect4, othello and gobang (is_scripted_player) as
+    selfplay.SCRIPTED_SEAT under the same conditions; with it off such an arena falls through to the reference."""
     if getattr(Arena, '_azg_native', False):
-        if (Arena._azg_raw_seats, Arena._azg_tree_free) == (raw_seats, tree_free_seats):
+        if (Arena._azg_raw_seats, Arena._azg_tree_free, Arena._azg_scripted) == (raw_seats, tree_free_seats, scripted_seats):
             return Arena
         Arena = Arena._azg_base                                      # (another choice of seats: wrap the reference's class afresh)
 
     class NativeArena(Arena):
         _azg_native = True
-        _azg_raw_seats, _azg_tree_free, _azg_base = raw_seats, tree_free_seats, Arena
+        _azg_raw_seats, _azg_tree_free, _azg_scripted, _azg_base = raw_seats, tree_free_seats, scripted_seats, Arena
 
         def _azg_seats(self, g):
-            """the seats of an arena with RandomPlayer / NNPlayer in it, or None: not every player is one this path accepts"""
-            from .selfplay import RANDOM_SEAT, PolicySeat
+            """the seats of an arena with RandomPlayer / NNPlayer / a scripted player in it, or None: not every player is one this path accepts"""
+            from .selfplay import RANDOM_SEAT, SCRIPTED_SEAT, PolicySeat, is_tree_free
             cache, seats = _NetCache(g, device), []
             for p in self.players:
-                kind, nn = tree_free_kind(p), getattr(p, 'nn', None)
+                kind, nn = tree_free_kind(p) if tree_free_seats else None, getattr(p, 'nn', None)
                 if kind == 'random':
                     seats.append(RANDOM_SEAT)
+                elif scripted_seats and is_scripted_player(p, self.game_cls):
+                    seats.append(SCRIPTED_SEAT)
                 elif kind == 'policy' and nn is not None:
                     a = getattr(p, 'args', None) or {}
                     seats.append(PolicySeat(cache.get(nn), a.get('startTemp'), a.get('temp_scaling_fn')))
@@ -180,13 +201,14 @@ def native_arena(Arena, *, device=None, raw_seats=True, tree_free_seats=False):
                     seats.append(cache.get(nn))
                 else:
                     return None
-            if not any(s is not None and not isinstance(s, PolicySeat) and s is not RANDOM_SEAT for s in seats):
+            if not any(s is not None and not is_tree_free(s) for s in seats):
                 return None                                          # (no network searched with MCTS: the engine has nothing to do)
             return seats
 
         def play_games(self, num, verbose=False, shuffle_players=True):          # Arena.pyx:188-376
             g = _ours(self.game_cls)
-            if tree_free_seats and g is not None and any(tree_free_kind(p) for p in self.players):
+            if g is not None and (tree_free_seats and any(tree_free_kind(p) for p in self.players)
+                                  or scripted_seats and any(is_scripted_player(p, self.game_cls) for p in self.players)):
                 ours = self._azg_seats(g)
                 if ours is None:
                     return Arena.play_games(self, num, verbose, shuffle_players)

@@ -1593,6 +1593,54 @@ extern "C" int azg_game_choose(void *stream, int game, int count, const azg_stat
     return AZG_OK;
 }
 
+extern "C" int azg_game_lookahead(void *stream, int game, int count, const azg_state *states, int32_t *num, int32_t *child_actions,
+                                  uint8_t *win, azg_state *children, void *obs, int obs_dtype) {
+    if (game < 0 || game >= k_num_games) return fail(AZG_E_INVALID_ARG, "unknown game id");
+    if (count < 0) return fail(AZG_E_INVALID_ARG, "count < 0");
+    if (!states) return fail(AZG_E_INVALID_ARG, "null states_dev");
+    if (!num) return fail(AZG_E_INVALID_ARG, "null num_dev");
+    if (!child_actions) return fail(AZG_E_INVALID_ARG, "null actions_dev");
+    if (obs_dtype < 0 || obs_dtype > 2) return fail(AZG_E_INVALID_ARG, "obs_dtype must be 0 (float32), 1 (float16) or 2 (float16 NHWC8)");
+    if (count == 0) return AZG_OK;
+    // grid (position, chunk of 64 children): connect4, tic-tac-toe, the 3-player env and othello are one wavefront per position
+    RULES_SWITCH(game, OBS_SWITCH(obs_dtype, obs,
+        hipLaunchKernelGGL((k_game_lookahead<G, OBS, NHWC8>), dim3(count, (G::MAXK + 63) / 64), dim3(64), 0, (hipStream_t)stream, count, states,
+                           num, child_actions, win, children, o)));
+    HIPCHK(hipGetLastError());
+    return AZG_OK;
+}
+
+// G::SCRIPTED and G::NAME of every game, by game id
+#define AZG_GAME_SCRIPTED(G_, ...) G_::SCRIPTED,
+static constexpr const char *k_game_scripted[] = {AZG_GAMES(AZG_GAME_SCRIPTED)};
+#define AZG_GAME_NAME(G_, ...) G_::NAME,
+static constexpr const char *k_game_names[] = {AZG_GAMES(AZG_GAME_NAME)};
+
+extern "C" const char *azg_game_scripted_player(int game) {
+    if (game < 0 || game >= k_num_games) { fail(AZG_E_INVALID_ARG, "unknown game id"); return nullptr; }
+    return k_game_scripted[game];
+}
+
+#define AZG_SCRIPTED_CASE(G_, ...) case G_::ID: if constexpr (G_::SCRIPTED != nullptr) { using G = G_; __VA_ARGS__; } break;
+extern "C" int azg_game_choose_scripted(void *stream, int game, int count, const azg_state *states, const double *u, int32_t *actions,
+                                        int32_t *status) {
+    if (game < 0 || game >= k_num_games) return fail(AZG_E_INVALID_ARG, "unknown game id");
+    if (count < 0) return fail(AZG_E_INVALID_ARG, "count < 0");
+    if (!states) return fail(AZG_E_INVALID_ARG, "null states_dev");
+    if (!u) return fail(AZG_E_INVALID_ARG, "null u_dev");
+    if (!actions) return fail(AZG_E_INVALID_ARG, "null actions_dev");
+    if (!status) return fail(AZG_E_INVALID_ARG, "null status_dev");
+    if (!k_game_scripted[game]) return fail(AZG_E_UNSUPPORTED, std::string("the reference has no scripted player for ") + k_game_names[game]);
+    if (count == 0) return AZG_OK;
+    switch (game) {
+        AZG_GAMES(AZG_SCRIPTED_CASE,
+            hipLaunchKernelGGL((k_game_choose_scripted<G>), dim3(count), dim3(64), 0, (hipStream_t)stream, count, states, u, actions, status))
+        default: break;
+    }
+    HIPCHK(hipGetLastError());
+    return AZG_OK;
+}
+
 extern "C" int azg_game_symmetries(void *stream, int game, int count, const azg_state *states, const float *pi, azg_state *sym_states,
                                    float *sym_obs, float *sym_pi) {
     if (game < 0 || game >= k_num_games) return fail(AZG_E_INVALID_ARG, "unknown game id");

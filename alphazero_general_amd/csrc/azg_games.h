@@ -23,6 +23,11 @@ struct C4 {
     static constexpr int A = 7, H = 6, W = 7, CELLS = 42, P = 2, HAS_DRAW = 1, MAX_TURNS = 42, NSYM = 2;
     static constexpr int OBS_C = 4, OBS = OBS_C * CELLS, MAXK = 7;
     static constexpr int SYM_RAW = 0;                                    // symmetries()[SYM_RAW] is the position itself
+    // The reference's scripted baseline player of this game (k_game_choose_scripted, azg_rules.h), or nullptr.  Such a game gives
+    // scripted_key(parent, child), the sort key of one move; the player takes the smallest key, and of the moves that share it the lowest
+    // action, or, with SCRIPTED_DRAWS, one drawn uniformly.
+    static constexpr const char *SCRIPTED = "OneStepLookaheadConnect4Player";
+    static constexpr bool SCRIPTED_DRAWS = true;
     struct S { uint64_t b0, b1; int player, turns; };
 
     static AZG_DEV S load(const azg_state *st, int lane) {
@@ -67,6 +72,12 @@ struct C4 {
         if (has4(s.b1)) return 2;
         if (valid_mask(s) == 0) return 4;
         return 0;
+    }
+    // OneStepLookaheadConnect4Player.play (connect4/players.py:43-49): ws = win_state() of the child; ws[parent's mover]: the win set
+    // (0), else ws[child's mover]: the stop-loss set (1), else the fallback set (2)
+    static AZG_DEV int scripted_key(const S &parent, const S &child) {
+        const int ws = win_bits(child);
+        return (ws >> parent.player) & 1 ? 0 : (ws >> child.player) & 1 ? 1 : 2;
     }
     // lane i < k receives the i-th valid action in ascending order
     static AZG_DEV int valid_list(const S &s, int lane, int *act_lds, int (&my_a)[1]) {
@@ -130,6 +141,7 @@ struct BR {
     static constexpr int ID = AZG_GAME_BRANDUBH;
     static constexpr const char *NAME = "brandubh";
     static constexpr bool SPARSE_HEADS = true;
+    static constexpr const char *SCRIPTED = nullptr;                     // no scripted baseline player (k_game_choose_scripted refuses the game)
     static constexpr int A = 588, H = 7, W = 7, CELLS = 49, P = 2, HAS_DRAW = 1, MAX_TURNS = 100, NSYM = 8;
     static constexpr int OBS_C = 5, OBS = OBS_C * CELLS, MAXK = 96;      // 8 attackers x 12 destinations bounds the move list
     static constexpr int SYM_RAW = 6;                                    // the identity: rot90^4 without flip (fastafl.pyx:213-256, k = 2*(4-1) + 0)
@@ -360,6 +372,7 @@ struct TM {
     static constexpr int ID = AZG_GAME_TRIMOK;
     static constexpr const char *NAME = "trimok";
     static constexpr bool SPARSE_HEADS = true;
+    static constexpr const char *SCRIPTED = nullptr;                     // no scripted baseline player (k_game_choose_scripted refuses the game)
     static constexpr int A = 25, H = 5, W = 5, CELLS = 25, P = 3, HAS_DRAW = 1, MAX_TURNS = 25, NSYM = 1;
     static constexpr int OBS_C = 5, OBS = OBS_C * CELLS, MAXK = 25;
     static constexpr int SYM_RAW = 0;
@@ -448,6 +461,8 @@ struct OT {
     static constexpr int OBS_C = 1, OBS = OBS_C * CELLS, MAXK = 60;      // at most 60 empty squares: one wavefront holds the move list
     static constexpr int SYM_RAW = 7;                                    // the identity is the LAST entry of symmetries() (k = 2*(4-1) + 1)
     static constexpr uint64_t COL0 = 0x0101010101010101ULL, COL7 = 0x8080808080808080ULL;
+    static constexpr const char *SCRIPTED = "GreedyOthelloPlayer";
+    static constexpr bool SCRIPTED_DRAWS = false;
     struct S { uint64_t b0, b1; int player, turns; };                    // b0: colour 1 (player 0), b1: colour -1
 
     // one step of the 8 directions (OthelloLogic.pyx:24); d = 0..7, x = bit >> 3, y = bit & 7
@@ -517,6 +532,13 @@ struct OT {
         const int own = __popcll(s.player == 0 ? s.b0 : s.b1), opp = __popcll(s.player == 0 ? s.b1 : s.b0);
         return own > opp ? 1 << s.player : own < opp ? 1 << (s.player ^ 1) : 4;
     }
+    // GreedyOthelloPlayer.play (OthelloPlayers.py:37): -child._board.count_diff(child.player).  count_diff(color) sums pieces * color
+    // (OthelloLogic.pyx:59-69) and is handed the player INDEX, not the colour: 0 when the child's mover is player 0, the stones of
+    // colour -1 minus those of colour 1 when it is player 1
+    static AZG_DEV int scripted_key(const S &parent, const S &child) {
+        (void)parent;
+        return child.player == 0 ? 0 : __popcll(child.b1) - __popcll(child.b0);
+    }
     // lane i < k receives the i-th legal move in ascending order: the lane of a legal square pushes its index to the lane of its rank
     // (the legal squares below it: mbcnt), one ds_permute; the others push to lane 63, which nobody reads (k <= 60)
     static AZG_DEV int valid_list(const S &s, int lane, int *act_lds, int (&my_a)[1]) {
@@ -574,6 +596,8 @@ struct GB {
     static constexpr int OBS_C = 4, OBS = OBS_C * CELLS, MAXK = 225;     // every empty cell is legal
     static constexpr int SYM_RAW = 7;                                    // the identity is the LAST entry of symmetries(), as othello
     static constexpr uint64_t ROWS4 = 0x7FFF7FFF7FFF7FFFULL, ROWS3 = 0x00007FFF7FFF7FFFULL;     // the board's bits of words 0-2 / 3
+    static constexpr const char *SCRIPTED = "GreedyGobangPlayer";
+    static constexpr bool SCRIPTED_DRAWS = false;
     struct S { uint64_t b0[4], b1[4]; int player, turns; };              // b0: colour 1 (player 0), b1: colour -1
 
     static AZG_DEV int bit_of(int i) { return (i / 15) * 16 + i % 15; }  // cell -> packed bit
@@ -656,6 +680,12 @@ struct GB {
 #pragma unroll
         for (int w = 0; w < 4; w++) full = full && (s.b0[w] | s.b1[w]) == rows(w);
         return full ? 4 : 0;
+    }
+    // GreedyGobangPlayer.play (GobangPlayers.py:37): int(child.win_state()[child.player]) -- 1 when the child's mover holds the five
+    // that the scan meets first, which the move just played cannot have made
+    static AZG_DEV int scripted_key(const S &parent, const S &child) {
+        (void)parent;
+        return (win_bits(child) >> child.player) & 1;
     }
     // child i < k of the list is the i-th empty cell (ascending): the lane of every empty cell stores its cell number at its rank (the
     // empty cells below it) in act_lds, then lane l reads child c * 64 + l back
@@ -740,6 +770,7 @@ struct TT {
     static constexpr int ID = AZG_GAME_TICTACTOE;
     static constexpr const char *NAME = "tic-tac-toe";
     static constexpr bool SPARSE_HEADS = false;   // A = 9 is one output subtile, which the exact heads compute whole at the same cost
+    static constexpr const char *SCRIPTED = nullptr;                     // no scripted baseline player (k_game_choose_scripted refuses the game)
     static constexpr int A = 9, H = 3, W = 3, CELLS = 9, P = 2, HAS_DRAW = 1, MAX_TURNS = 9, NSYM = 8;
     static constexpr int OBS_C = 1, OBS = OBS_C * CELLS, MAXK = 9;
     static constexpr int SYM_RAW = 7;                                    // the identity is the LAST entry of symmetries(), as othello
@@ -840,6 +871,7 @@ struct HN {
     static constexpr int ID = AZG_GAME_HNEFATAFL;
     static constexpr const char *NAME = "hnefatafl";
     static constexpr bool SPARSE_HEADS = false;   // no network launch is built for this game at all
+    static constexpr const char *SCRIPTED = nullptr;                     // no scripted baseline player (k_game_choose_scripted refuses the game)
     static constexpr int A = 2420, H = 11, W = 11, CELLS = 121, P = 2, HAS_DRAW = 1, MAX_TURNS = 512, NSYM = 8;
     // MAXK bounds the move list of ANY board azg_set_states can hand over: every move lands on a cell that holds no piece, and a cell is
     // reached by at most one mover piece from each of the four directions, so with n mover pieces k <= min(20 n, 4 (121 - n)) <= 403

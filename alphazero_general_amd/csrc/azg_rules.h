@@ -99,6 +99,96 @@ __global__ __launch_bounds__(64) void k_game_choose(int count, const azg_state *
     if (lane == 0) { actions[i] = action; status[i] = action < 0 ? 1 : 0; }
 }
 
+// The children of states[i]: entry j < k of the position's own move list (valid_list: ascending, k clamped to MAXK) played with
+// G::play on a copy of the position, for j in the chunk blockIdx.y of 64 entries.  A position lives in the registers of one wavefront,
+// so a wavefront plays its children one after the other and the grid spreads them: (position, chunk), every wavefront rebuilding the
+// list (in act_lds, whatever the game's valid_list keeps there).  The games of at most 64 children are one wavefront per position.
+// num[i] = k; child_actions[i, j] the action, -1 from k on; of child j < k, where the pointer is given: win[i, j, 0:P+1], children[i, j],
+// obs[i, j] as k_game_step writes them.  Rows from k on are left alone.  The parent's win_state is not consulted (play_action does not).
+// An entry of the list indexes nothing but a register compare: it is played only when it lies in [0, A).
+template <class G, typename OT, bool NHWC8>
+__global__ __launch_bounds__(64) void k_game_lookahead(int count, const azg_state *states, int32_t *num, int32_t *child_actions, uint8_t *win,
+                                                       azg_state *children, OT *obs) {
+    constexpr int A = G::A, NV = G::P + 1, MAXK = G::MAXK, NCH = (MAXK + 63) / 64;
+    __shared__ int act_lds[NCH * 64];
+    const int i = blockIdx.x, chunk = blockIdx.y, lane = threadIdx.x;
+    if (i >= count || chunk >= NCH) return;
+    const typename G::S s = G::load(&states[i], lane);
+    int my_a[NCH];
+    int k = G::valid_list(s, lane, act_lds, my_a);
+    k = k < 0 ? 0 : k > MAXK ? MAXK : k;
+    wave_sync();
+#pragma unroll
+    for (int c = 0; c < NCH; c++) act_lds[c * 64 + lane] = c * 64 + lane < k ? my_a[c] : -1;
+    wave_sync();
+    if (chunk == 0 && lane == 0) num[i] = k;
+    const int j0 = chunk * 64;
+    if (j0 + lane < MAXK) child_actions[(size_t)i * MAXK + j0 + lane] = act_lds[j0 + lane];
+    const int j1 = k < j0 + 64 ? k : j0 + 64;
+    for (int j = j0; j < j1; j++) {
+        const int a = __builtin_amdgcn_readfirstlane(act_lds[j]);
+        if ((unsigned)a >= (unsigned)A) continue;
+        typename G::S t = s;
+        G::play(t, a);
+        const size_t o = (size_t)i * MAXK + j;
+        if (children) G::store(t, &children[o], lane);
+        if (win) {
+            const int ws = G::win_bits(t);                                   // (every lane: the tafl games ballot)
+            if (lane < NV) win[o * NV + lane] = (uint8_t)((ws >> lane) & 1);
+        }
+        if (obs) {
+            if constexpr (NHWC8) G::write_obs_nhwc8(t, (_Float16 *)obs + o * G::CELLS * 8, lane);
+            else G::template write_obs<OT>(t, obs + o * G::OBS, lane);
+        }
+    }
+}
+
+// The reference's scripted baseline player of the game (G::SCRIPTED) on states[i], one wavefront per position: every entry of the move
+// list is played on a copy and given G::scripted_key(parent, child); the move is the lowest action of the smallest key, or -- with
+// G::SCRIPTED_DRAWS, np.random.choice(list(set)) without p -- entry min(m - 1, (int)(u[i] * m)) of the m moves of the smallest key in
+// ascending order.  status 1 and action -1 without a valid move (the reference raises).  win_state of the parent is not consulted.
+template <class G>
+__global__ __launch_bounds__(64) void k_game_choose_scripted(int count, const azg_state *states, const double *u, int32_t *actions,
+                                                             int32_t *status) {
+    constexpr int A = G::A, MAXK = G::MAXK, NCH = (MAXK + 63) / 64;
+    __shared__ int act_lds[NCH * 64];
+    __shared__ int key_lds[G::SCRIPTED_DRAWS ? NCH * 64 : 1];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= count) return;
+    const typename G::S s = G::load(&states[i], lane);
+    int my_a[NCH];
+    int k = G::valid_list(s, lane, act_lds, my_a);
+    k = k < 0 ? 0 : k > MAXK ? MAXK : k;
+    wave_sync();
+#pragma unroll
+    for (int c = 0; c < NCH; c++) act_lds[c * 64 + lane] = c * 64 + lane < k ? my_a[c] : -1;
+    wave_sync();
+    int best = 0x7fffffff, best_a = -1, m = 0;                               // (wave-uniform: the smallest key, its first action, its count)
+    for (int j = 0; j < k; j++) {
+        const int a = __builtin_amdgcn_readfirstlane(act_lds[j]);
+        if ((unsigned)a >= (unsigned)A) continue;
+        typename G::S t = s;
+        G::play(t, a);
+        const int key = __builtin_amdgcn_readfirstlane(G::scripted_key(s, t));
+        if (key < best) { best = key; best_a = a; m = 0; }
+        if (key == best) m++;
+        if constexpr (G::SCRIPTED_DRAWS) { if (lane == 0) key_lds[j] = key; }
+    }
+    if constexpr (G::SCRIPTED_DRAWS) {
+        wave_sync();
+        if (m > 1) {
+            int idx = (int)(u[i] * (double)m);
+            idx = idx < 0 ? 0 : idx > m - 1 ? m - 1 : idx;                   // (u outside [0, 1) or NaN is outside the contract: still a move of the set)
+            for (int j = 0, seen = 0; j < k; j++) {
+                const int a = __builtin_amdgcn_readfirstlane(act_lds[j]);
+                if ((unsigned)a >= (unsigned)A || key_lds[j] != best) continue;
+                if (seen++ == idx) { best_a = a; break; }
+            }
+        }
+    }
+    if (lane == 0) { actions[i] = best_a; status[i] = best_a < 0 ? 1 : 0; }
+}
+
 // GameState.symmetries(pi) (Game.py:100-113) of states[i], entry k = blockIdx.y of the reference's list: the arithmetic of k_emit_samples.
 template <class G>
 __global__ __launch_bounds__(64) void k_game_symmetries(int count, const azg_state *states, const float *pi, azg_state *sym_states,

@@ -4,8 +4,9 @@ azg_game_symmetries (include/azg.h).  What it is for: evaluating a net on a batc
 GenericPlayers.py:55-97), expanding stored (state, pi) samples into their symmetries at training time, writing another search.
 
 A position is one row of a uint8 tensor [n, 80]: the bytes of an azg_state.  `pack` / `unpack` / `to_games` convert from and to host
-objects (this package's envs, the reference's own classes, or (cells, player, turns[, aux0]) tuples); `step`, `symmetries` and `choose`
-(the move of a player without a tree: RandomPlayer, NNPlayer) are one kernel launch each on torch's current stream, read nothing back and, given `out=`, allocate nothing -- so a play loop can be captured
+objects (this package's envs, the reference's own classes, or (cells, player, turns[, aux0]) tuples); `step`, `symmetries`, `choose`
+(the move of a player without a tree: RandomPlayer, NNPlayer), `lookahead` (the children of every position, one ply) and
+`choose_scripted` (the reference's scripted baseline player of the game) are one kernel launch each on torch's current stream, read nothing back and, given `out=`, allocate nothing -- so a play loop can be captured
 in a graph.  There is no CPU path for the rules themselves: `step` / `symmetries` need a HIP device."""
 import collections
 import ctypes as C
@@ -21,6 +22,7 @@ STATE_BYTES = C.sizeof(_abi.State)                              # 80
 Step = collections.namedtuple('Step', 'next valid win obs status')
 Symmetries = collections.namedtuple('Symmetries', 'states obs pi')
 Choice = collections.namedtuple('Choice', 'actions status')
+Lookahead = collections.namedtuple('Lookahead', 'num actions win children obs')
 _OBS_FORMS = {torch.float32: 0, torch.float16: 1, 'nhwc8': 2}
 
 
@@ -35,6 +37,9 @@ class DeviceGames:
         self.A, self.P, self.NV, self.NSYM = gi.action_size, gi.num_players, gi.num_players + 1, gi.num_symmetries
         self.obs_shape = (gi.obs_c, gi.obs_h, gi.obs_w)
         self.cells = gi.cells
+        self.max_children = gi.max_children
+        name = self.L.azg_game_scripted_player(self.game)
+        self.scripted_player = None if name is None else name.decode()   # the reference's scripted baseline player (class name), or None
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
         self.device = torch.device(device)
@@ -171,4 +176,52 @@ class DeviceGames:
         with torch.cuda.device(self.device):
             _abi.check(self.L.azg_game_choose(_stream(), self.game, n, _ptr(states), _ptr(policy), _ptr(temp), _ptr(u), _ptr(b_actions),
                                               _ptr(b_status)))
+        return Choice(b_actions[:n], b_status[:n])
+
+    def lookahead(self, states, *, win=True, children=False, obs=None, out=None):
+        """the children of every position, one ply (azg_game_lookahead): the position's own move list -- valid_moves in ascending action
+        order, k <= K = max_children entries -- played entry by entry with play_action on a copy, as a Lookahead record:
+          num      int32 [n]           k                                actions  int32 [n, K]        the action of child j; -1 for j >= k
+          win      uint8 [n, K, P + 1] win_state of child j             children uint8 [n, K, 80]    the child positions
+          obs      observation of child j in the formats of `step`: [n, K, C, H, W] or, 'nhwc8', [n, K, H*W, 8]
+        Rows j >= k of win / children / obs are left as they were (zero in a new tensor); an output whose flag is false is None.  The
+        parent's win_state is not consulted: a finished position that still has moves has children.  out: a Lookahead whose tensors are
+        written instead of new ones (they may hold more than n rows); none of them may be `states`.  perft is a loop of it:
+            frontier = dg.initial(1)
+            for depth in range(d):
+                la = dg.lookahead(frontier, children=True)
+                live = (la.actions >= 0) & (la.win.sum(2) == 0)        # children that exist and are not finished
+                frontier = la.children[live]"""
+        states = self._rows(states)
+        n, K = states.shape[0], self.max_children
+        assert obs is None or obs in _OBS_FORMS, 'obs: None, torch.float32, torch.float16 or \'nhwc8\''
+        o = out if out is not None else Lookahead(None, None, None, None, None)
+        b_num = self._buf(o.num, True, 'num', n, (), torch.int32)
+        b_act = self._buf(o.actions, True, 'actions', n, (K,), torch.int32)
+        b_win = self._buf(o.win, win, 'win', n, (K, self.NV), torch.uint8)
+        b_ch = self._buf(o.children, children, 'children', n, (K, STATE_BYTES), torch.uint8)
+        b_obs = self._buf(o.obs, obs is not None, 'obs', n, (K,) + self.obs_tail(obs), torch.float32 if obs == torch.float32 else torch.float16)
+        assert b_ch is None or b_ch.data_ptr() != states.data_ptr(), 'out.children must not be `states`'
+        with torch.cuda.device(self.device):
+            _abi.check(self.L.azg_game_lookahead(_stream(), self.game, n, _ptr(states), _ptr(b_num), _ptr(b_act), _ptr(b_win), _ptr(b_ch),
+                                                 _ptr(b_obs), _OBS_FORMS.get(obs, 0)))
+        return Lookahead(*[None if b is None else b[:n] for b in (b_num, b_act, b_win, b_ch, b_obs)])
+
+    def choose_scripted(self, states, u=None, out=None):
+        """the move of the reference's scripted baseline player of this game (`scripted_player`: OneStepLookaheadConnect4Player,
+        GreedyOthelloPlayer, GreedyGobangPlayer; azg_game_choose_scripted, include/azg.h for each player's rule) on every position, as a
+        Choice record.  u float64 [n] in [0, 1): connect4 plays element min(m - 1, int(u[i] * m)) of the m moves of its chosen set in
+        ascending order; the other two consume none; u=None draws torch.rand on the device.  status 1 with action -1 where there is no
+        valid move (the reference raises); a game without a scripted player raises AzgError (AZG_E_UNSUPPORTED)."""
+        states = self._rows(states)
+        n = states.shape[0]
+        o = out if out is not None else Choice(None, None)
+        if u is None:
+            u = torch.rand(n, dtype=torch.float64, device=self.device)
+        assert isinstance(u, torch.Tensor) and u.dtype == torch.float64 and u.device == self.device, 'u: float64 on the device'
+        assert tuple(u.shape) == (n,) and u.is_contiguous(), 'u: contiguous [n]'
+        b_actions = self._buf(o.actions, True, 'actions', n, (), torch.int32)
+        b_status = self._buf(o.status, True, 'status', n, (), torch.int32)
+        with torch.cuda.device(self.device):
+            _abi.check(self.L.azg_game_choose_scripted(_stream(), self.game, n, _ptr(states), _ptr(u), _ptr(b_actions), _ptr(b_status)))
         return Choice(b_actions[:n], b_status[:n])

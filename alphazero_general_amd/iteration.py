@@ -324,7 +324,7 @@ def lead(op, game_cls, nnets, args, *, iteration=0, folder=None, num_games=None,
         from .selfplay import PolicySeat, is_tree_free
         uniq, index, seats = [], [], []                              # (gating: [new] + [past] * (P - 1) -- every distinct net travels once)
         for seat in nnets:
-            # a tree-free seat (selfplay.RANDOM_SEAT, PolicySeat) travels with the command: RANDOM_SEAT as it is, a PolicySeat as its start
+            # a tree-free seat (selfplay.RANDOM_SEAT, SCRIPTED_SEAT, PolicySeat) travels with the command: the first two as they are, a PolicySeat as its start
             # temperature and iterated schedule, its network with the weights like any other
             n = seat.net if isinstance(seat, PolicySeat) else None if is_tree_free(seat) else seat
             seats.append(PolicySeat(None, seat.start_temp, None, seat.table(game_cls, args).tolist()) if isinstance(seat, PolicySeat)
@@ -360,7 +360,7 @@ def serve(game_cls, device=None, group=None):
         uniq = [_net_from(game_cls, D.broadcast_state_dict(None, m, group=group), na, dev) for na, m in zip(cmd['net_args'], cmd['meta'])]
         nnets = [uniq[j] if j >= 0 else None for j in cmd['index']]
         from .selfplay import PolicySeat
-        for i, seat in enumerate(cmd.get('seats') or []):            # tree-free seats: RANDOM_SEAT as sent, a PolicySeat around its network
+        for i, seat in enumerate(cmd.get('seats') or []):            # tree-free seats: RANDOM_SEAT / SCRIPTED_SEAT as sent, a PolicySeat around its network
             if isinstance(seat, PolicySeat):
                 nnets[i] = PolicySeat(nnets[i], seat.start_temp, None, seat.temp_table)
             elif seat is not None:

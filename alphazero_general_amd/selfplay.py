@@ -46,6 +46,30 @@ def _random_seat():
 RANDOM_SEAT = _RandomSeat()
 
 
+class _ScriptedSeat:
+    """an arena seat that plays the reference's scripted baseline player of the arena's game (DeviceGames.scripted_player:
+    OneStepLookaheadConnect4Player, GreedyOthelloPlayer, GreedyGobangPlayer): one ply of lookahead, no network, no tree"""
+
+    def __repr__(self):
+        return 'SCRIPTED_SEAT'
+
+    def __reduce__(self):                                            # (one object per process, as RANDOM_SEAT)
+        return (_scripted_seat, ())
+
+    def __eq__(self, other):
+        return isinstance(other, _ScriptedSeat)
+
+    def __hash__(self):
+        return hash('SCRIPTED_SEAT')
+
+
+def _scripted_seat():
+    return SCRIPTED_SEAT
+
+
+SCRIPTED_SEAT = _ScriptedSeat()
+
+
 class PolicySeat:
     """an arena seat that plays NNPlayer.play (GenericPlayers.py:55-97): one evaluation of `net` per move, masked, raised to
     1 / temperature and sampled -- no tree.  start_temp / temp_scaling_fn: the player's args.startTemp and args.temp_scaling_fn (:59, :73;
@@ -66,7 +90,7 @@ class PolicySeat:
 
 
 def is_tree_free(seat):
-    return isinstance(seat, (_RandomSeat, PolicySeat))
+    return isinstance(seat, (_RandomSeat, _ScriptedSeat, PolicySeat))
 
 
 class _Lane:
@@ -383,7 +407,8 @@ class ArenaRunner:
     policy float32(1 / A) for every action and value zeros.
     RANDOM_SEAT or a PolicySeat entry is a tree-free seat (RandomPlayer / NNPlayer, GenericPlayers.py:47-97): the search sees it as a raw
     seat and its tree is ignored; after the search DeviceGames.choose picks its move from the root states and advance(actions=...) plays
-    it, re-rooting every tree of the game as Arena.pyx:170-171 does with player.update.  Its np.random.choice uniform is
+    it, re-rooting every tree of the game as Arena.pyx:170-171 does with player.update.  SCRIPTED_SEAT is the game's scripted baseline
+    player (DeviceGames.choose_scripted), refused for a game that has none.  Its np.random.choice uniform is
     u53(tape(seed ^ TREEFREE_SEED_XOR, TREEFREE_STREAM + global slot, round)): independent of how the games are sharded.  Rounds with
     tree-free seats run eagerly (use_graph is ignored).
 
@@ -397,6 +422,8 @@ class ArenaRunner:
         self.tree_free = [is_tree_free(n) for n in self.seats_given]
         self.nnets = [None if tf else n for n, tf in zip(self.seats_given, self.tree_free)]   # (the search: a tree-free seat is a raw seat)
         self.game = azg_game_id(game_cls)
+        if any(isinstance(n, _ScriptedSeat) for n in self.seats_given) and _abi.lib().azg_game_scripted_player(int(self.game)) is None:
+            raise NotImplementedError('SCRIPTED_SEAT: the reference ships no scripted player for %s' % game_cls.__module__)
         self.B = int(num_slots)
         P = game_cls.num_players()
         assert len(self.nnets) == P
@@ -472,6 +499,7 @@ class ArenaRunner:
         dev = lambda rows, dt: torch.tensor(np.asarray(rows), dtype=dt, device=e.device)
         self._tf_seat = dev([[m[p] for p in range(P)] for m in perms], torch.int64)                      # [B, P] player -> seat
         self._tf_random = [mi for mi, seat in enumerate(self.seats_given) if isinstance(seat, _RandomSeat)]
+        self._tf_scripted = [mi for mi, seat in enumerate(self.seats_given) if isinstance(seat, _ScriptedSeat)]
         self._tf_u = torch.zeros(self.B, dtype=torch.float64, device=e.device)
         self._tf_none = torch.full((self.B,), -1, dtype=torch.int32, device=e.device)
         self._tf_policy = []                                         # (seat index, net, temperature table [P, turns] on the device)
@@ -516,6 +544,12 @@ class ArenaRunner:
             for mi in self._tf_random:
                 israndom |= seat == mi
             actions = torch.where(israndom, pick(c), actions)
+        if self._tf_scripted:
+            c = self.games.choose_scripted(states, u)
+            isscripted = torch.zeros_like(seat, dtype=torch.bool)
+            for mi in self._tf_scripted:
+                isscripted |= seat == mi
+            actions = torch.where(isscripted, pick(c), actions)
         for mi, net, tab in self._tf_policy:
             temp = tab[mover.clamp(0, tab.shape[0] - 1), turns.clamp(0, tab.shape[1] - 1)].contiguous()
             c = self.games.choose(states, self._seat_policy(net, states), temp, u)

@@ -480,6 +480,45 @@ int  azg_game_choose(void *stream, int game, int count, const azg_state *states_
                      const double *u_dev     /*[count], the uniform np.random.choice draws, in [0, 1)*/,
                      int32_t *actions_dev    /*[count]*/, int32_t *status_dev /*[count]*/);
 
+/* The children of every position, one ply (within ABI v7), under the contract of azg_game_step: every argument judged first
+ * (AZG_E_INVALID_ARG for an unknown game, count < 0, a null states_dev / num_dev / actions_dev, an obs_dtype outside 0..2; count == 0:
+ * AZG_OK, nothing launched), stream-ordered, no host read, no allocation.  For position i < count the position's own move list --
+ * valid_moves() in ascending action order, k entries, k <= MAXK = azg_game_info.max_children (clamped in the kernel) -- is played entry
+ * by entry with play_action on a copy of the position: num_dev[i] = k; actions_dev[i, j] the action of child j, -1 for j >= k; and of
+ * child j < k, each output whose pointer is not NULL: win_dev[i, j, 0:P+1] its win_state(), children_dev[i, j] its azg_state,
+ * obs_dev[i, j] its observation() in the three formats of azg_game_step.  Rows j >= k of win / children / obs are left alone.  The
+ * parent's win_state is not consulted (play_action does not consult it: a finished position that still has moves has children).  The
+ * outputs must not alias states_dev.  The grid is (position, chunk of 64 children): every wavefront rebuilds the move list and plays
+ * its chunk, so the games of at most 64 children are one wavefront per position and hnefatafl's 448 spread over seven. */
+int  azg_game_lookahead(void *stream, int game, int count, const azg_state *states_dev, int32_t *num_dev /*[count]*/,
+                        int32_t *actions_dev /*[count, MAXK]*/, uint8_t *win_dev /*[count, MAXK, P+1]*/,
+                        azg_state *children_dev /*[count, MAXK]*/, void *obs_dev /*[count, MAXK, ...]*/, int obs_dtype /*0, 1, 2*/);
+
+/* The class name of the scripted baseline player the reference ships for `game` -- "OneStepLookaheadConnect4Player",
+ * "GreedyOthelloPlayer", "GreedyGobangPlayer" -- or NULL: a game without one, or (with AZG_E_INVALID_ARG in azg_last_error) an unknown
+ * game id.  No device needed. */
+const char *azg_game_scripted_player(int game);
+
+/* That player's move on every position (within ABI v7): one launch, one wavefront per position, contract and status convention of
+ * azg_game_choose (AZG_E_INVALID_ARG for an unknown game, count < 0, a null states_dev / u_dev / actions_dev / status_dev), then
+ * AZG_E_UNSUPPORTED for a game whose azg_game_scripted_player is NULL, then count == 0: AZG_OK; nothing is launched in any of these.
+ * Each player is the reference's loop of clone / play_action over the valid moves, quirks included:
+ *   connect4  OneStepLookaheadConnect4Player.play (envs/connect4/players.py:32-69): ws = win_state() of the child; ws[the parent's mover]
+ *             puts the move in the win set, else ws[the child's mover] in the stop-loss set, else in the fallback set; the move is drawn
+ *             from the first non-empty of the three.  (The stop-loss test asks whether the opponent has won AFTER the mover's own move:
+ *             from a reachable position it never holds, so the player does not block a threat.)  The draw is np.random.choice(list(set))
+ *             without p, which in numpy is randint on the list's length and NOT the one-uniform choice of azg_game_choose: here it is
+ *             element min(m - 1, (int)(u_dev[i] * m)), in double, of the m moves of the set in ascending action order.
+ *   othello   GreedyOthelloPlayer.play (envs/othello/OthelloPlayers.py:28-40): the smallest (-count_diff(child.player), action).
+ *             count_diff(color) sums pieces * color (OthelloLogic.pyx:59-69) and is handed the player index: the key is 0 when the
+ *             child's mover is player 0 (the lowest valid action is played), and the stones of colour -1 minus those of colour 1 when
+ *             it is player 1.  u_dev is not consumed.
+ *   gobang    GreedyGobangPlayer.play (envs/gobang/GobangPlayers.py:28-40): the smallest (int(child.win_state()[child.player]), action).
+ *             u_dev is not consumed.
+ * status_dev[i] = 0 and actions_dev[i] the move; status 1 and action -1 for a position without a valid move (the reference raises). */
+int  azg_game_choose_scripted(void *stream, int game, int count, const azg_state *states_dev,
+                              const double *u_dev /*[count], in [0, 1)*/, int32_t *actions_dev /*[count]*/, int32_t *status_dev /*[count]*/);
+
 /* ---- timing hooks for bench.py (HIP events on `stream` around the engine's own kernels) -------------------- */
 int  azg_profile_enable(azg_engine *e, int on);
 /* accumulated GPU ms + launch counts per kernel family: select, backup, advance. blocking. */
